@@ -26,7 +26,11 @@ Workloads (BASELINE.json `configs`):
               (deephar_amd/parallel.py).  `collective_us` is the all-gather's share of a step (HIP events).
 One step is timed with the inputs already resident in HBM and the outputs left in HBM: value = frames all ranks
 processed / max-over-ranks wall time of exactly K steps bracketed by barriers + device synchronisation.
-Rank 0 prints ONE JSON line, which also carries
+A plain run sets up, runs W untimed and K timed steps, and prints ONE JSON line from rank 0 (`value`, `ms_per_step`, ...).
+    --dump-outputs DIR  after the timed steps, rank 0 writes every model output of the last step (what a caller of the
+                        timed path receives) as DIR/output_<k>.npy, float32, in model order; same arguments, same inputs.
+    --full              everything beyond the headline figure as well (below); --dump-steps also runs the per-kernel pass.
+With --full the line also carries
   roofline     : the dominant kernel by summed time (an MFMA conv instantiation, named as rocprofv3 names it):
                  algorithmic FLOPs per launch (from the plan: 2 * M * K * Cout) / average launch duration, measured
                  with HIP events on the launch stream in an eager pass right after the timed region (kernels inside
@@ -39,6 +43,8 @@ Rank 0 prints ONE JSON line, which also carries
                  frames and for raw uint8 frames (normalised inside the first convolution).  Never `value`.
   cpu_baseline : the CPU oracle (a port; TensorFlow/Keras are not installable here) on the host cores of this box:
                  batch 16, median of 5 after one warm-up.  N=1, rank 0 only.
+  and the mpii line's bf16x3, frame_sharded_clips and compact h36m / ntu_spnet / speed2d legs, speed2d's per-block
+  protocol and the clip workloads' serial-form comparison (--no-* options drop them one by one).
 """
 import argparse
 import json
@@ -662,6 +668,31 @@ def timed(step, streams, steps, warmup, world, pairs=None):
 
 LAST_TIMED = {}
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(model, bound, clips):
+    """Every model output of the last step, in model order (device tensors): what a caller of the timed path receives."""
+    if clips:
+        return list(LAST_SCM[0].last_outputs)
+    bp = bound[0][0]
+    return [bp.tensor(v) for v in model.plan.outputs]
+
+
+def dump_outputs(path, tensors):
+    """DIR/output_<k>.npy, float32.  Over DUMP_LIMIT_BYTES in all, an output larger than its even share of the limit is
+    replaced by a fixed sample of its flattened elements (seeded, sorted indices: the same positions from run to run)."""
+    import torch
+    arrays = [np.ascontiguousarray(t.detach().to(torch.float32).cpu().numpy()) for t in tensors]
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays) > DUMP_LIMIT_BYTES
+    os.makedirs(path, exist_ok=True)
+    for k, a in enumerate(arrays):
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(k).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, 'output_%02d.npy' % k), a)
+
 
 def per_rank_table(world, collective_us):
     """Every rank's {rank, ms_per_step (own clock), host_enqueue_us_per_step, collective_us} gathered to all ranks."""
@@ -760,6 +791,11 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workload', choices=sorted(WORKLOADS), default='mpii')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: per-kernel pass and roofline, '
+                         'CPU baseline, Model.predict boundary, bf16x3 / clip / compact legs, speed2d protocol, serial form')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write every model output of the last timed step to DIR/output_<k>.npy (float32)')
     ap.add_argument('--batch', type=int, default=None, help='frames (mpii) or clips (clip workloads) per GPU per step')
     ap.add_argument('--blocks', type=int, default=8, help='mpii only')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -934,11 +970,14 @@ def main():
         return
 
     dt = timed(step, streams, args.steps, args.warmup, world, pairs)
+    ms_per_step = 1e3 * dt / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(model, bound, wl['clips']))
     serial_ms = None
     if wl['clips']:
         collective_us = round(1e3 * float(np.mean([a.elapsed_time(b) for a, b in pairs])), 2)
     per_rank = per_rank_table(world, collective_us)           # (a collective: every rank calls it)
-    if wl['clips'] and (world > 1 or args.force_collective):
+    if args.full and wl['clips'] and (world > 1 or args.force_collective):
         serial_ms = serial_form_ms(LAST_SCM[0], step, streams, pairs, world)
 
     # sanity: outputs finite and in range
@@ -946,17 +985,18 @@ def main():
     ok = bool(np.all(np.isfinite(pose)) and pose[..., :2].min() >= 0 and pose[..., :2].max() <= 1)
 
     # ---- per-kernel pass (HIP events on the launch stream) ----------------------------------------------
-    restage()
-    rows, kinds = profile_plans(bound)
-    ms_per_step = 1e3 * dt / args.steps
-    roof, extra = roofline(rows, kinds, flops_per_step, ms_per_step)
-    roof['launches_per_forward'] = real_launches(bound)      # (plan steps minus those absorbed by grouped / paired launches)
-    roof['plan_steps'] = len(rows)
+    roof, extra, rows = None, {}, []
+    if args.full or args.dump_steps:
+        restage()
+        rows, kinds = profile_plans(bound)
+        roof, extra = roofline(rows, kinds, flops_per_step, ms_per_step)
+        roof['launches_per_forward'] = real_launches(bound)      # (plan steps minus those absorbed by grouped / paired launches)
+        roof['plan_steps'] = len(rows)
 
-    # The default line also measures the opt-in split-bf16 GEMM mode (Model.gemm_precision = 'bf16x3'): same model, same
+    # The full line also measures the opt-in split-bf16 GEMM mode (Model.gemm_precision = 'bf16x3'): same model, same
     # batch, same timing; reported under "bf16x3", never as `value` (the headline stays on the fp32-MFMA path).
     split_leg = None
-    if args.workload == 'mpii' and model.gemm_precision == 'f32' and not args.no_bf16x3:
+    if args.full and args.workload == 'mpii' and model.gemm_precision == 'f32' and not args.no_bf16x3:
         sm = wl['build'](args.blocks)
         sm.gemm_precision = 'bf16x3'
         if args.streams is not None:
@@ -992,10 +1032,10 @@ def main():
             split_leg['predict_fps_f32'], split_leg['predict_fps_u8'] = sfps['f32'], sfps['u8']
         del sm
 
-    # The default (mpii) line also carries a short run of the frame-sharded clip path, so that a multi-GPU run of the
+    # The full (mpii) line also carries a short run of the frame-sharded clip path, so that a multi-GPU run of the
     # contract command exercises the RCCL all-gather leg as well (BASELINE.json configs[3]); every rank takes part.
     clip_leg = None
-    if args.workload == 'mpii' and not args.no_clip_leg:
+    if args.full and args.workload == 'mpii' and not args.no_clip_leg:
         cw = WORKLOADS['penn_merge']
         cstep, cpairs, _, cstreams, cframes, _, ccheck, cpar, _ = setup_clips('penn_merge', cw['build'](), cw['per_gpu'],
                                                                              world, rank, args)
@@ -1023,8 +1063,8 @@ def main():
 
     # [r06] ... and, at N = 1, compact legs of the other BASELINE configurations and of the reference's speed protocol
     extra_legs = {}
-    if args.workload == 'mpii' and world == 1 and not args.no_extra_legs and not args.no_clip_leg and args.input == 'f32' \
-            and model.gemm_precision == 'f32':
+    if args.full and args.workload == 'mpii' and world == 1 and not args.no_extra_legs and not args.no_clip_leg \
+            and args.input == 'f32' and model.gemm_precision == 'f32':
         for w in ('h36m', 'ntu_spnet', 'speed2d'):
             extra_legs[w] = compact_leg(w, args, rank)
 
@@ -1052,8 +1092,10 @@ def main():
                        'hipgraph': not args.no_graph, 'streams': model.plan.nstreams, 'input': args.input,
                        'gemm': model.gemm_precision,
                        'outputs_finite_in_range': ok},
-            'roofline': roof,
+            'full': args.full,
         }
+        if roof is not None:
+            out['roofline'] = roof
         out.update(extra)
         out['per_rank'] = per_rank
         if collective_us is not None:
@@ -1072,15 +1114,15 @@ def main():
         if split_leg is not None:
             out['bf16x3'] = split_leg
         out.update(extra_legs)
-        if args.workload == 'mpii' and world == 1 and not args.no_predict:
+        if args.full and args.workload == 'mpii' and world == 1 and not args.no_predict:
             fps = predict_boundary(model, per_gpu, args.predict_frames)
             out['predict_fps_f32'], out['predict_fps_u8'] = fps['f32'], fps['u8']
             out['predict_note'] = 'Model.predict on host numpy arrays, %d frames in batches of %d, wall clock incl. ' \
                                   'H2D of the frames and D2H of all outputs, after one warm-up call' % (
                                       args.predict_frames, per_gpu)
-        if args.workload == 'speed2d' and world == 1 and not args.no_predict:
+        if args.full and args.workload == 'speed2d' and world == 1 and not args.no_predict:
             out['speed2d'] = speed2d_protocol(full_model, args, model.executor.tune_table)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(full_model if full_model is not None else model, args.workload, args.blocks)
         if args.dump_steps:
             dump = [dict(kind=s.kind, name=s.name, kernel=kernel_name(s) if s.kind == 'conv' else s.kind,

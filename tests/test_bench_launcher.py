@@ -81,3 +81,43 @@ def test_rank_major_gather_view_orders_frames():
     dst = torch.empty(2, 6, 4, 2)
     dst.view(2, 2, 3, 4, 2).copy_(v[..., 1:3])                   # what run_device does with a strided head input
     assert torch.equal(dst, full[..., 1:3])
+
+
+def test_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output in model order; past the size limit an output larger than its
+    share becomes a fixed sample of its elements, the same from run to run."""
+    code = ("import sys, torch, bench\n"
+            "bench.DUMP_LIMIT_BYTES = 4096\n"
+            "outs = [torch.arange(6, dtype=torch.float64).reshape(2, 3), torch.linspace(0, 1, 4000).reshape(40, 100)]\n"
+            "bench.dump_outputs(sys.argv[1], outs)\n"
+            "bench.dump_outputs(sys.argv[2], outs)\n")
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    r = subprocess.run([sys.executable, '-c', code, str(a), str(b)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    import numpy as np
+    assert sorted(os.listdir(str(a))) == ['output_00.npy', 'output_01.npy']
+    small, big = np.load(str(a / 'output_00.npy')), np.load(str(a / 'output_01.npy'))
+    assert small.dtype == np.float32 and np.array_equal(small, np.arange(6, dtype=np.float32).reshape(2, 3))
+    assert big.dtype == np.float32 and big.shape == (2048 // 4,) and np.all(np.diff(big) > 0)
+    assert np.array_equal(big, np.load(str(b / 'output_01.npy')))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run times exactly --steps steps, prints the headline fields only, and --dump-outputs writes every model
+    output of the last step (finite, float32, batch-leading)."""
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--blocks', '2', '--batch', '4', '--steps', '3',
+                        '--warmup', '1', '--dump-outputs', str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=540)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _one_json_line(r.stdout)
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in line
+    assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0 and line['full'] is False
+    assert not {'roofline', 'cpu_baseline', 'bf16x3', 'frame_sharded_clips', 'predict_fps_f32', 'h36m'} & set(line)
+    import numpy as np
+    files = sorted(os.listdir(str(tmp_path)))
+    assert files == ['output_%02d.npy' % k for k in range(len(files))] and len(files) >= 2
+    for f in files:
+        a = np.load(str(tmp_path / f))
+        assert a.dtype == np.float32 and a.shape[0] == 4 and np.all(np.isfinite(a))

@@ -2,7 +2,7 @@
 # A/B of planner / library switches on the GPU box: tools/ab_bench.sh <tag> <workload> [ENV=VAL ...] -> one summary line
 TAG=$1; W=$2; shift 2
 OUT=${GRAFT_REPO_ROOT:-.}/gpurun_out
-env "$@" python bench.py --workload $W --steps 30 --warmup 5 --no-cpu-baseline --no-predict --no-clip-leg --no-bf16x3 \
+env "$@" python bench.py --full --workload $W --steps 30 --warmup 5 --no-cpu-baseline --no-predict --no-clip-leg --no-bf16x3 \
     --dump-steps $OUT/${TAG}_steps_$W.json > $OUT/${TAG}_line_$W.json 2> $OUT/${TAG}_err_$W.log
 python - <<PY
 import json

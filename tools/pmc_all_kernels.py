@@ -37,7 +37,7 @@ def main():
     for w in sys.argv[1:]:
         steps = os.path.join(OUT, 'pmcall_steps_%s.json' % w)
         tune = os.path.join(OUT, 'pmcall_tune_%s.json' % w)
-        base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', w, '--tune-cache', tune] + LIGHT + \
+        base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--workload', w, '--tune-cache', tune] + LIGHT + \
             ['--no-graph', '--steps', '2', '--warmup', '1']
         subprocess.call(base + ['--dump-steps', steps], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=ROOT)
         dump = [s for s in json.load(open(steps)) if not s.get('absorbed')]

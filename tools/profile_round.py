@@ -131,7 +131,7 @@ def main():
         tune = os.path.join(OUT, '%s_tune_%s.json' % (args.tag, w))
         if os.path.exists(tune):
             os.remove(tune)
-        base = [py, bench, '--workload', w, '--tune-cache', tune] + args.bench_args.split()
+        base = [py, bench, '--full', '--workload', w, '--tune-cache', tune] + args.bench_args.split()
         # (1) the line (full default line for mpii: predict boundary, bf16x3 and clip legs, CPU baseline)
         log = os.path.join(OUT, '%s_bench_%s.log' % (args.tag, w))
         sh(base + ['--steps', str(args.steps), '--warmup', '3', '--dump-steps', os.path.join(OUT, '%s_steps_%s.json' % (args.tag, w))],
