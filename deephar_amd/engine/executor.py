@@ -207,7 +207,7 @@ class BoundPlan:
         own argument struct before the weights are packed -- a layer is never bound with a packing its launch rejects."""
         if getattr(self.plan, 'gemm_precision', 'f32') == 'bf16x3' and self.lib.dh_conv2d_split_eligible(C.byref(args)):
             return 1
-        if os.environ.get('DEEPHAR_HALO_CONV', '1') != '0' and self.lib.dh_conv2d_halo_eligible(C.byref(args)):
+        if self.plan.rules.halo_conv and self.lib.dh_conv2d_halo_eligible(C.byref(args)):
             return 2
         return 0
 
@@ -511,8 +511,8 @@ class BoundPlan:
         launched back to back on one stream, reads the same tensor and is small enough to be bound by the cost of a node
         rather than by its work into ONE launch (dh_conv2d_dw_group_f32: bit-identical, the work-groups of one grid run
         either kernel's code).  The depthwise entry of `calls` stays as a no-op so that step indices (event waits, per-step
-        profiles) keep their meaning.  DEEPHAR_GROUP_LAUNCHES=0 switches it off.  Returns the number of pairs merged."""
-        if os.environ.get('DEEPHAR_GROUP_LAUNCHES', '1') == '0' or self.grouped or self.paired:
+        profiles) keep their meaning.  Switch: plan.rules.group_launches.  Returns the number of pairs merged."""
+        if not self.plan.rules.group_launches or self.grouped or self.paired:
             return self.grouped
         lib = self.lib
         for i in range(self.npre, len(self.calls) - 1):
@@ -526,28 +526,31 @@ class BoundPlan:
             fd, ad, sd = self.calls[j]
             if sc.kind != 'conv' or sd.kind != 'dwconv' or sd.wait or i in self.noop_calls or fc is lib.dh_conv2d_dw_group_f32:
                 continue
-            xc, xd = sc.ins['x'], sd.ins['x']
-            if xc.buf is not xd.buf or any(v is not None and v.buf is sc.outs['y'].buf for v in sd.ins.values()):
-                continue                               # not the same input, or the depthwise conv reads the conv's result
+            # which pairs: the two halves of one unit, both reading its input.  Whether they may run as one grid is the pair
+            # path's test: neither reads or overwrites what the other writes (the memory plan re-uses space: the depthwise
+            # result must not lie over the convolution's residuals either)
+            if sc.ins['x'].buf is not sd.ins['x'].buf or not self._independent(sc, sd):
+                continue
             ca, da = ac[0]._obj, ad[0]._obj
             if ca.N * ca.OH * ca.OW > self.GROUP_MAX_ROWS or da.N * da.H * da.W * da.C > self.GROUP_MAX_DW_ELEMS:
                 continue
             if lib.dh_conv2d_dw_group_f32(ac[0], ad[0], stream_ptr) != 0:      # (a real launch: the pair's own outputs)
                 continue
-            sc.attrs['grouped'] = True                 # (for bench.py's kernel names: the plan's steps are shared by every
-            self.calls[i] = (lib.dh_conv2d_dw_group_f32, (ac[0], ad[0]), sc)      # batch size it is bound to -- what counts
-            self.calls[j] = (_noop_launch, (), sd)                                 # for execution is `calls` / `noop_calls`)
-            self.noop_calls.add(j)
-            self.absorbed[i] = sd
+            sc.attrs['grouped'] = True                 # (for bench.py's kernel names: the plan's steps are shared by every batch
+            self._absorb(i, j, lib.dh_conv2d_dw_group_f32)     # size it is bound to -- `calls` / `noop_calls` count for execution)
             self.grouped += 1
         self._pair_skinny_convs(stream_ptr)
-        if (self.grouped or self.paired) and self.graph is not None:
-            if self.plan.nstreams > 1:
-                _GRAPH_GRAVEYARD.append(self.graph)
-            else:
-                lib.dh_graph_destroy(self.graph)
-            self.graph = None
+        if self.grouped or self.paired:
+            self._drop_graph()
         return self.grouped
+
+    def _absorb(self, i, k, fn):
+        """Launch i becomes the two-struct launch `fn` over its own and launch k's arguments; k stays as a no-op."""
+        (_, ai, si), (_, ak, sk) = self.calls[i], self.calls[k]
+        self.calls[i] = (fn, (ai[0], ak[0]), si)
+        self.calls[k] = (_noop_launch, (), sk)
+        self.noop_calls.add(k)
+        self.absorbed[i] = sk
 
     PAIR_LOOKAHEAD = 3              # launches of the same stream a partner may be pulled forward past
 
@@ -580,8 +583,8 @@ class BoundPlan:
         work-groups of one grid run either convolution's own code: bit-identical).  The partner is the next launch of the same
         stream, or one up to PAIR_LOOKAHEAD launches further down that is independent of everything it is pulled past; it must
         wait for no event itself and pass no launch that does (an event a launch waits for may be the one that orders the
-        partner's inputs too).  DEEPHAR_PAIR_CONVS=0 switches it off."""
-        if os.environ.get('DEEPHAR_PAIR_CONVS', '1') == '0':
+        partner's inputs too).  Switch: plan.rules.pair_convs."""
+        if not self.plan.rules.pair_convs:
             return
         lib = self.lib
 
@@ -607,10 +610,7 @@ class BoundPlan:
                     break
                 if skinny(k) and self._independent(sa, sk) and all(self._independent(q, sk) for q in passed) and \
                         lib.dh_conv2d_pair_f32(aa[0], ak[0], stream_ptr) == 0:
-                    self.calls[i] = (lib.dh_conv2d_pair_f32, (aa[0], ak[0]), sa)
-                    self.calls[k] = (_noop_launch, (), sk)
-                    self.noop_calls.add(k)
-                    self.absorbed[i] = sk
+                    self._absorb(i, k, lib.dh_conv2d_pair_f32)
                     self.paired.append((i, k))
                     break
                 passed.append(sk)
@@ -733,12 +733,7 @@ class BoundPlan:
             self.calls[i] = (fn, (args[0], table[sig]), step)
         lib.dh_event_destroy(e0)
         lib.dh_event_destroy(e1)
-        if self.graph is not None:
-            if self.plan.nstreams > 1:
-                _GRAPH_GRAVEYARD.append(self.graph)      # see __del__
-            else:
-                lib.dh_graph_destroy(self.graph)
-            self.graph = None
+        self._drop_graph()
         return table
 
     def profile(self, stream_ptr, reps=1):
@@ -764,19 +759,22 @@ class BoundPlan:
             lib.dh_event_destroy(e)
         return times / reps
 
-    def __del__(self):
+    def _drop_graph(self):
         # ROCm 7.2: hipGraphExecDestroy of a graph captured across several streams (event fork/join nodes) leaves
         # the runtime in a state where a LATER capture + launch of another multi-stream graph segfaults
         # (tools/repro_seg.py: two bound plans of one model destroyed, next model's first replay crashes; the
         # same sequence with one stream, or without the destroy, is fine).  Multi-stream graph execs are therefore
         # parked until process exit instead of destroyed -- a few KB of kernel-node parameters each.
+        if self.graph is not None:
+            if self.plan.nstreams > 1:
+                _GRAPH_GRAVEYARD.append(self.graph)
+            else:
+                self.lib.dh_graph_destroy(self.graph)
+            self.graph = None
+
+    def __del__(self):
         try:
-            if self.graph is not None:
-                if self.plan.nstreams > 1:
-                    _GRAPH_GRAVEYARD.append(self.graph)
-                else:
-                    self.lib.dh_graph_destroy(self.graph)
-                self.graph = None
+            self._drop_graph()
         except Exception:
             pass
 

@@ -39,6 +39,8 @@ Fusion rules (what the reference leaves to TensorFlow as separate kernels):
                 skinny-conv kernel (the head's second residual unit, spnet.py:139-141) is not written out: that kernel reads
                 concatenate([pool(x), x2]) in place (dh_conv2d_seg_f32).  Bit-identical.
   (R10 / R10b / R10c: sibling convolutions of one tensor merged into one launch -- see the passes below.)
+Every rule that can be switched off has a field in engine/rules.py (RuleSet); a plan is built under ONE RuleSet (build_plan)
+and records it as Plan.rules.
 All tensors are fp32; sizes are tracked per batch item so one plan serves any batch size.
 """
 import os
@@ -46,6 +48,7 @@ import os
 import numpy as np
 
 from .. import graph as G
+from .rules import RuleSet
 
 
 class Buf:
@@ -187,7 +190,11 @@ class Plan:
         self.params = []       # ordered unique graph.Param list
         self.nstreams = 1
         self.gemm_precision = 'f32'   # 'bf16x3': eligible convs run split-bf16 on the bf16 matrix cores (executor)
-        self.split_adds = True        # rule R9 / second-add rule applied (Planner: DEEPHAR_SPLIT_ADDS, read once)
+        self.rules = RuleSet()        # the rule switches the plan was built under (build_plan: read once, recorded here)
+
+    @property
+    def split_adds(self):
+        return self.rules.split_adds
 
     def total_flops(self, n=1):
         return sum(s.flops(n) for s in self.steps)
@@ -222,21 +229,21 @@ class _PoolView:
 
 
 class Planner:
-    def __init__(self, inputs, outputs, nstreams=1, stream_policy='list'):
+    def __init__(self, inputs, outputs, nstreams=1, stream_policy='list', rules=RuleSet()):
+        self.rules = rules
         self.nstreams = nstreams
         self.stream_policy = stream_policy
         self.producer = {}            # id(Value) -> the Step that writes it
         self.g_inputs = inputs
         self.g_outputs = outputs
         self.nodes = G.topo_nodes(outputs)
-        # R9 and the second-add rule re-associate fp32 sums (conv + a + b for the reference's a + b + conv), so the switch
-        # -- it exists for A/B measurements -- is read ONCE per plan and recorded in it: a plan is built
-        # entirely under one setting, and Plan.split_adds says which.
-        self.split_adds = os.environ.get('DEEPHAR_SPLIT_ADDS', '1') != '0'
-        if self.split_adds:
+        # R9 and the second-add rule re-associate fp32 sums (conv + a + b for the reference's a + b + conv), R11 the two
+        # residual additions: the switches -- they exist for A/B measurements -- are read ONCE per plan (build_plan) and
+        # recorded in it: a plan is built entirely under one RuleSet, and Plan.rules says which.
+        if self.rules.split_adds:
             self.nodes = self._split_wide_adds(self.nodes, outputs)
         self.plan = Plan()
-        self.plan.split_adds = self.split_adds
+        self.plan.rules = self.rules
         self.val = {}          # tensor uid -> Value | _Lazy
         self.absorbed = set()  # node uids folded into another step
         self.consumers = {}
@@ -401,9 +408,9 @@ class Planner:
     def _virtual_upsample_ok(self, node):
         """True when every reader of this UpSampling2D((2, 2)) output reaches, through BatchNormalization / ReLU only, a
         plain 1x1 convolution or a separable convolution: those read the half-resolution tensor directly (the 1x1
-        convolution runs BEFORE the up-sampling, the depthwise convolution up-samples on load).  DEEPHAR_UP_COMMUTE=0: off."""
+        convolution runs BEFORE the up-sampling, the depthwise convolution up-samples on load).  Switch: RuleSet.up_commute."""
         t = node.outputs[0]
-        if os.environ.get('DEEPHAR_UP_COMMUTE', '1') == '0' or len(t.shape) < 3 or node.attrs.get('size', (2, 2)) != (2, 2):
+        if not self.rules.up_commute or len(t.shape) < 3 or node.attrs.get('size', (2, 2)) != (2, 2):
             return False
         seen, stack, ends = set(), [t], 0
         while stack:
@@ -417,7 +424,7 @@ class Planner:
                         stack.append(n.outputs[0])
                 elif n.op == 'conv' and (n.attrs['kh'], n.attrs['kw'], n.attrs.get('sh', 1), n.attrs.get('sw', 1)) == (1, 1, 1, 1):
                     ends += 1
-                elif self._skinny_conv_node(n, t.shape[-1]) and os.environ.get('DEEPHAR_RESAMPLE_ON_LOAD', '1') != '0':
+                elif self._skinny_conv_node(n, t.shape[-1]) and self.rules.resample_on_load:
                     ends += 1          # R12: the skinny-conv kernel up-samples on load (dh_conv_args.x_resample = 1)
                 elif n.op == 'sepconv' and (n.attrs.get('sh', 1), n.attrs.get('sw', 1)) == (1, 1):
                     ends += 1
@@ -436,9 +443,9 @@ class Planner:
         """The concatenate whose buffer t's producer writes into (R4): t's only consumer -- or [r05, R4b] the only
         concatenate among consumers that all read strided views.  SPNet's heat-map head (spnet.py:24-48): `pred_maps` goes
         to the channel soft-max AND into concatenate([fw_maps, pred_maps]); written where the concatenation wants it, the
-        soft-argmax kernel reads it there (pitch 2 J) and the copy launch disappears.  DEEPHAR_CONCAT_SHARED=0: off."""
+        soft-argmax kernel reads it there (pitch 2 J) and the copy launch disappears.  Switch: RuleSet.concat_shared."""
         cat = self.sole_consumer(t, 'concat')
-        if cat is not None or self.out_uids.get(t.uid, 0) or os.environ.get('DEEPHAR_CONCAT_SHARED', '1') == '0':
+        if cat is not None or self.out_uids.get(t.uid, 0) or not self.rules.concat_shared:
             return cat
         cs = [n for n, _ in self.consumers.get(t.uid, [])]
         cats = [n for n in cs if n.op == 'concat']
@@ -502,8 +509,8 @@ class Planner:
         are one 32-column tile (two 16-column tiles on the skinny kernel), each output column keeps its own K order, so the
         result is bit-identical and a launch is saved per prediction block.  (Round 4 tried the same on the 64 -> 96 | 48
         pairs of the entry flow -- widths that tile worse together than apart; this rule only merges slabs that stay
-        inside the family rule of their parts and carry no epilogue.)  DEEPHAR_MERGE_HEADS=0 switches it off."""
-        if os.environ.get('DEEPHAR_MERGE_HEADS', '1') == '0':
+        inside the family rule of their parts and carry no epilogue.)  Switch: RuleSet.merge_heads."""
+        if not self.rules.merge_heads:
             return
         same = ('sh', 'sw', 'Cin', 'pre_relu', 'post_relu', 'up2', 'res2_down')
 
@@ -526,7 +533,7 @@ class Planner:
                     if st.attrs['kh'] % 2 == 0 or st.attrs['kw'] % 2 == 0 or st.attrs['pt'] != st.attrs['kh'] // 2 or \
                             st.attrs['pl'] != st.attrs['kw'] // 2 or st.attrs['Cin'] % 16 == 0:
                         return False
-                if os.environ.get('DEEPHAR_MERGE_KXK', '1') == '0':
+                if not self.rules.merge_kxk:
                     return False
             if set(a.params) - {'w', 'pre_bn'} or set(b.params) - {'w', 'pre_bn'} or \
                     a.params.get('pre_bn') is not b.params.get('pre_bn'):
@@ -584,8 +591,8 @@ class Planner:
         has moves into the prologue of that part's readers (convolutions reading it as their input: relu on load = relu on
         store).  Same products, same chains: bit-identical.  Only inside one kernel family (the skinny-conv rule must say
         the same for the parts and the whole: round 4 measured that the wide pairs of the entry flow tile worse together
-        than apart).  DEEPHAR_MERGE_SIBLINGS=0 switches it off."""
-        if os.environ.get('DEEPHAR_MERGE_SIBLINGS', '1') == '0':
+        than apart).  Switch: RuleSet.merge_siblings."""
+        if not self.rules.merge_siblings:
             return
         steps = self.plan.steps
 
@@ -691,8 +698,8 @@ class Planner:
         `concat_tensorlist([x1, x2, xa])`): two launches over two [frames, joints, 160] tensors.  Their producers write the two
         channel runs of ONE joint buffer instead and a single pooling launch covers both -- pooling is per channel, so every
         output element is the maximum of the same values.  Bit-identical; one launch less per action head (the latency
-        regime: a node costs ~5 us whatever it moves).  DEEPHAR_MERGE_POOLS=0 switches it off."""
-        if os.environ.get('DEEPHAR_MERGE_POOLS', '1') == '0':
+        regime: a node costs ~5 us whatever it moves).  Switch: RuleSet.merge_pools."""
+        if not self.rules.merge_pools:
             return
         steps = self.plan.steps
 
@@ -756,8 +763,8 @@ class Planner:
         the unit's merged shortcut | conv1 launch (R10c), a layer of the skinny-conv kernel.  That kernel takes the maximum of
         the window while it gathers the first c_split channels of its input and reads the rest where they are
         (dh_conv2d_seg_f32): the pooled tensor is never written, one launch less per head.  Bit-identical.
-        DEEPHAR_POOL_SEGMENTS=0 switches it off."""
-        if os.environ.get('DEEPHAR_POOL_SEGMENTS', '1') == '0':
+        Switch: RuleSet.pool_segments."""
+        if not self.rules.pool_segments:
             return
         steps = self.plan.steps
         i = 0
@@ -803,7 +810,7 @@ class Planner:
         """t = a convolution's output after its own BN / first residual add.  -> (add node, upsample node, b) when t's
         only consumer is add([t, UpSampling2D(b)]) with b at half resolution and the same channels, else None."""
         a2 = self.sole_consumer(t, 'add')
-        if a2 is None or len(a2.inputs) != 2 or len(t.shape) < 3 or os.environ.get('DEEPHAR_RES2_DOWN', '1') == '0':
+        if a2 is None or len(a2.inputs) != 2 or len(t.shape) < 3 or not self.rules.res2_down:
             return None                          # (the switch exists for A/B measurements of the rule)
         other = [x for x in a2.inputs if x.uid != t.uid]
         if len(other) != 1:
@@ -947,7 +954,7 @@ class Planner:
                     epi['res2_down'] = True
                     self.absorbed.update((a2.uid, up.uid))
                     t = a2.outputs[0]
-            if (epi['res1'] is None) != (epi['res2'] is None) and self.split_adds:
+            if (epi['res1'] is None) != (epi['res2'] is None) and self.rules.split_adds:
                 # a second two-operand add behind the first (SPNet: add([residual_unit(x), lateral]), spnet.py:303 on top of
                 # common.py:67): the free residual slot takes it -- (conv + shortcut) + lateral, the reference's order (with
                 # a half-resolution shortcut in the second slot, R11: (conv + lateral) + shortcut)
@@ -1006,7 +1013,7 @@ class Planner:
         if isinstance(x, _UpView):
             if x.full is None and (a['kh'], a['kw'], a.get('sh', 1), a.get('sw', 1)) == (1, 1, 1, 1) and len(out_t.shape) >= 3:
                 return self._emit_conv_before_upsampling(x, pre_bn, pre_relu, param, a, out_t, name)
-            if x.full is None and will_be_skinny and os.environ.get('DEEPHAR_RESAMPLE_ON_LOAD', '1') != '0':
+            if x.full is None and will_be_skinny and self.rules.resample_on_load:
                 x, resample = x.low, 1           # R12: the skinny-conv kernel reads the half-resolution tensor up-sampled
             else:
                 x = self._realize_up(x)
@@ -1146,7 +1153,7 @@ class Planner:
         # BatchNormalization / ReLU -- is a convolution on the skinny-conv kernel is not written out: that kernel takes the
         # maximum (+ minimum) of the four pixels while it loads its input (dh_conv_args.x_resample = 2 / 3).  The action
         # head's `conv2h` on max_min_pooling(x1) (spnet.py:77-84): one launch less per head.
-        if os.environ.get('DEEPHAR_RESAMPLE_ON_LOAD', '1') != '0' and len(x.shape) >= 3 and a.get('mode', 0) in (0, 1) and \
+        if self.rules.resample_on_load and len(x.shape) >= 3 and a.get('mode', 0) in (0, 1) and \
                 (a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']) == (2, 2, 2, 2, 0, 0) and x.shape[-3] % 2 == 0 and \
                 x.shape[-2] % 2 == 0:
             reader = self._only_reader_through_bn_relu(node.outputs[0])
@@ -1158,15 +1165,15 @@ class Planner:
         # second output (dh_conv_args.y_pool) -- the stand-alone pool reads the whole tensor back from HBM
         # (reception.py:105-116: every hourglass level is used at full AND at half resolution).  Bit-identical.  Neutral
         # while the pool ran beside other work on a second stream (round 2); on ONE stream, where the forward is the sum
-        # of its kernels, it is worth 1-2 % on the MPII model.  DEEPHAR_FUSE_POOL=0 switches it off.
+        # of its kernels, it is worth 1-2 % on the MPII model.  Switch: RuleSet.fuse_pool.
         # [r06] also at 16 and 8 columns (a wave's 32 output rows are two / four whole image rows there: it pools alone) --
-        # one dependent launch less per down-scaling unit of SPNet's pyramids (DEEPHAR_FUSE_POOL_SMALL=0: 32 columns only).
+        # one dependent launch less per down-scaling unit of SPNet's pyramids (RuleSet.fuse_pool_small off: 32 columns only).
         prod = self.producer.get(id(x))
-        if os.environ.get('DEEPHAR_FUSE_POOL', '1') != '0' and prod is not None and prod.kind == 'conv' and \
+        if self.rules.fuse_pool and prod is not None and prod.kind == 'conv' and \
                 prod.outs.get('y') is x and 'ypool' not in prod.outs and not prod.attrs.get('up2') and \
                 a.get('mode', 0) == 0 and (a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']) == (2, 2, 2, 2, 0, 0) and \
                 (x.shape[-2] == 32 or (x.shape[-2] in (8, 16) and (x.shape[-3] * x.shape[-2]) % 32 == 0 and
-                                       os.environ.get('DEEPHAR_FUSE_POOL_SMALL', '1') != '0')) and \
+                                       self.rules.fuse_pool_small)) and \
                 x.shape[-3] % 2 == 0 and x.C % 4 == 0 and x.ld % 4 == 0 and y.ld % 4 == 0 and \
                 x.coff % 4 == 0 and y.coff % 4 == 0 and \
                 not (prod.attrs['kh'] * prod.attrs['kw'] > 1 and prod.attrs['Cin'] % 32 == 16) and \
@@ -1257,7 +1264,7 @@ class Planner:
                 self.absorbed.add(sm.uid)
         # [r06] multiply([p, c]) right behind a read-out whose coordinates and confidence have no other reader (the replica
         # read-out in front of an action head, spnet.py:108) is folded into it: xy receives (x, y) * confidence
-        if os.environ.get('DEEPHAR_FOLD_POSE_MUL', '1') != '0' and len(twins) == 1 and 'xy' in outs and 'conf_prob' in outs:
+        if self.rules.fold_pose_mul and len(twins) == 1 and 'xy' in outs and 'conf_prob' in outs:
             xy_t = next((n.outputs[0] for n, _ in self.consumers.get(twins[0].outputs[0].uid, []) if n.op == 'expect2d'), None)
             cf_t = next((n.outputs[0] for n, _ in self.consumers.get(twins[0].outputs[0].uid, []) if n.op == 'jointprob'), None)
             mul = self.sole_consumer(xy_t, 'mul') if xy_t is not None else None
@@ -1443,11 +1450,13 @@ class Planner:
         self.plan.params = out
 
 
-def build_plan(inputs, outputs, nstreams=1, gemm_precision='f32', stream_policy='list'):
+def build_plan(inputs, outputs, nstreams=1, gemm_precision='f32', stream_policy='list', rules=None):
+    """rules: the RuleSet the plan is built and later bound under; None = RuleSet.from_env(), read here, once."""
+    rules = RuleSet.from_env() if rules is None else rules
     if gemm_precision not in ('f32', 'bf16x3'):
         raise ValueError("gemm_precision must be 'f32' or 'bf16x3', got %r" % (gemm_precision,))
     if stream_policy not in ('list', 'tail'):
         raise ValueError("stream_policy must be 'list' or 'tail', got %r" % (stream_policy,))
-    plan = Planner(inputs, outputs, nstreams, stream_policy).run()
+    plan = Planner(inputs, outputs, nstreams, stream_policy, rules).run()
     plan.gemm_precision = gemm_precision
     return plan

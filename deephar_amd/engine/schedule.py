@@ -104,7 +104,7 @@ def stream_unassigned(k, j):
     return k > j
 
 
-def assign_streams_tail(plan, deps, items=2, nstreams=2):
+def assign_streams_tail(plan, deps, items=2, nstreams=2, floor_us=30.0, shift=0):
     """Streams for the LATENCY regime (a couple of clips per call: exp/pennaction/eval_speed2d.py).  Stream 1 takes a
     SUFFIX A = steps [s, n) of the planner's order: a suffix of a topological order is closed under "is read by", so every
     cross-stream dependency points from stream 0 to stream 1 -- one direction, no ping-pong (the list scheduler above
@@ -137,10 +137,8 @@ def assign_streams_tail(plan, deps, items=2, nstreams=2):
     # 20 ... 40 -> 3.96 ... 3.99, 60 -> 4.03, 100 -> 4.05 (profiles/r06_tail_policy_calibration.txt): the split is mostly a
     # balance of launch COUNTS.  (Also tried there: a critical-path-first order and a backbone-first order in front of the
     # suffix search -- 4.8-5.2 ms and 4.2-4.3 ms: the suffix of the planner's own block-by-block order is the best of the
-    # three.)  DEEPHAR_TAIL_FLOOR_US overrides it for such sweeps.
-    import os
-    floor = float(os.environ.get('DEEPHAR_TAIL_FLOOR_US', '30'))
-    cost = [floor + max(st.flops(items) / 90e12, st.bytes(items) / 3e12) * 1e6 for st in plan.steps]
+    # three.)  `floor_us` is that constant (RuleSet.tail_floor_us overrides it for such sweeps).
+    cost = [floor_us + max(st.flops(items) / 90e12, st.bytes(items) / 3e12) * 1e6 for st in plan.steps]
     consumers = [[] for _ in range(n)]
     for j, d in enumerate(deps):
         for i in d:
@@ -194,8 +192,7 @@ def assign_streams_tail(plan, deps, items=2, nstreams=2):
             best_s, best, best_placed = s, span, placed
     if best_s == 0 or best > 0.95 * serial:
         return stream, order
-    shift = int(os.environ.get('DEEPHAR_TAIL_SHIFT', '0'))       # A/B aid: move the start of the suffix by this many steps
-    if shift:
+    if shift:                                                    # A/B aid (RuleSet.tail_shift): move the start of the suffix
         best_s = min(max(best_s + shift, 1), n - 1)
         best, best_placed = simulate(best_s)
     if nstreams >= 3:
@@ -319,10 +316,11 @@ def allocate(plan, reach):
 def finalize(plan, nstreams=1, policy='list'):
     """Fill step.stream / step.wait (cross-stream dependencies) and place every buffer in the arena.
     policy: 'list' = the list scheduler (throughput regime: branches of an hourglass), 'tail' = assign_streams_tail (two
-    streams, latency regime)."""
+    streams, latency regime; its two constants come from plan.rules)."""
     deps = compute_deps(plan)
     if policy == 'tail' and nstreams >= 2:
-        stream, order = assign_streams_tail(plan, deps, nstreams=nstreams)
+        stream, order = assign_streams_tail(plan, deps, nstreams=nstreams, floor_us=plan.rules.tail_floor_us,
+                                            shift=plan.rules.tail_shift)
         if order != list(range(len(order))):
             plan.steps[:] = [plan.steps[j] for j in order]
             deps = compute_deps(plan)

@@ -55,6 +55,9 @@ class Model:
         # GEMM-shaped convs split their fp32 operands exactly into three bf16 parts and run six partial products on the
         # bf16 matrix cores with fp32 accumulation (csrc/gemm1x1s.hip): same accuracy class, ~1.7x faster, not bit-identical
         self.gemm_precision = __import__('os').environ.get('DEEPHAR_GEMM', 'f32')
+        # the engine's rule switches (engine/rules.py: RuleSet) the plan is built and bound under; None: read from the
+        # environment when the plan is built (RuleSet.from_env).  The plan records them either way: self.plan.rules
+        self.rules = None
         # validates connectivity early (raises like Keras' "graph disconnected")
         self._nodes = G.topo_nodes(self.outputs)
         reach = {t.uid for t in self.inputs}
@@ -81,6 +84,7 @@ class Model:
     gemm_precision = _engine_option('gemm_precision')
     num_streams = _engine_option('num_streams')
     stream_policy = _engine_option('stream_policy')
+    rules = _engine_option('rules')
     del _engine_option
 
     # ---- Keras-like attributes -----------------------------------------------------------------------
@@ -212,7 +216,7 @@ class Model:
         if self._plan is None:
             from .engine.planner import build_plan
             self._plan = build_plan(self.inputs, self.outputs, nstreams=self.num_streams,
-                                    gemm_precision=self.gemm_precision, stream_policy=self.stream_policy)
+                                    gemm_precision=self.gemm_precision, stream_policy=self.stream_policy, rules=self.rules)
         return self._plan
 
     @property

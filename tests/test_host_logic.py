@@ -170,6 +170,7 @@ def test_planner_wide_adds_become_conv_epilogues(monkeypatch):
     m1 = build()
     plan = m1.plan
     assert base.split_adds is False and plan.split_adds is True      # read once per plan, recorded in it
+    assert base.rules.split_adds is False and plan.rules.split_adds is True
     adds = lambda p: [s for s in p.steps if s.kind == 'eltwise' and s.attrs.get('op', 0) == 0 and 'b' in s.ins]
     # (a sum that became a convolution's epilogue can also carry the pooling behind it: rule R7 -- those launches go too)
     npool = lambda p: sum(1 for s in p.steps if s.kind == 'conv' and 'ypool' in s.outs)
@@ -615,6 +616,32 @@ def test_heat_map_head_rules_on_the_host(monkeypatch):
     assert sum(s.flops() for s in plan.steps) == pytest.approx(sum(s.flops() for s in base.steps))
 
 
+def test_ruleset_from_env():
+    """engine/rules.py: field x of RuleSet is the variable DEEPHAR_X; unset = the default, a boolean rule is on unless the
+    value is the string '0', the two numbers of the 'tail' policy parse as float / int; the result is frozen."""
+    import dataclasses
+    from deephar_amd.engine.rules import RuleSet
+    fields = dataclasses.fields(RuleSet)
+    assert len(fields) == 18
+    default = RuleSet.from_env({})
+    assert default == RuleSet() and default.tail_floor_us == 30.0 and default.tail_shift == 0
+    flags = [f.name for f in fields if f.type is bool]
+    assert len(flags) == 16 and all(getattr(default, n) is True for n in flags)
+    for n in flags:
+        got = RuleSet.from_env({'DEEPHAR_' + n.upper(): '0'})
+        assert getattr(got, n) is False and got == dataclasses.replace(default, **{n: False})      # (that one alone)
+        for on in ('1', '', 'off', 'false', '00', ' 0'):                                              # only the string '0' is off
+            assert RuleSet.from_env({'DEEPHAR_' + n.upper(): on}) == default, (n, on)
+    nums = RuleSet.from_env({'DEEPHAR_TAIL_FLOOR_US': '10', 'DEEPHAR_TAIL_SHIFT': '-1', 'DEEPHAR_STREAMS': '2', 'merge_kxk': '0'})
+    assert nums == RuleSet(tail_floor_us=10.0, tail_shift=-1)
+    assert isinstance(nums.tail_floor_us, float) and isinstance(nums.tail_shift, int)
+    assert RuleSet.from_env({'DEEPHAR_TAIL_FLOOR_US': '7.5'}).tail_floor_us == 7.5
+    with pytest.raises(ValueError):
+        RuleSet.from_env({'DEEPHAR_TAIL_SHIFT': '1.5'})                                               # int(), as before
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        default.merge_kxk = False
+
+
 def test_round6_planner_rules_on_the_host(monkeypatch):
     """[r06] Rules R10b (K x K siblings as one centred-kernel convolution), R10c (sibling 1x1 convolutions into a joint buffer,
     per-column affine, ReLU moved to the reader), R11 (UpSampling2D in front of an up-scaling unit: the shortcut runs at half
@@ -623,6 +650,7 @@ def test_round6_planner_rules_on_the_host(monkeypatch):
     import bench
     from deephar_amd import Model, weights
     from deephar_amd.engine.planner import ConcatAffine, ConcatParam
+    from deephar_amd.engine.rules import RuleSet
 
     def plan(**env):
         for k in ('DEEPHAR_MERGE_KXK', 'DEEPHAR_MERGE_SIBLINGS', 'DEEPHAR_UP_COMMUTE', 'DEEPHAR_RESAMPLE_ON_LOAD', 'DEEPHAR_FOLD_POSE_MUL',
@@ -635,6 +663,23 @@ def test_round6_planner_rules_on_the_host(monkeypatch):
                   DEEPHAR_FOLD_POSE_MUL='0', DEEPHAR_MERGE_POOLS='0', DEEPHAR_FUSE_POOL_SMALL='0', DEEPHAR_POOL_SEGMENTS='0')
     m, on = plan()
     assert len(off.steps) == 604 and len(on.steps) == 413
+    # a plan records the rules it was built under: `off` was built before the environment went back to all-on
+    all_off = dict(merge_kxk=False, merge_siblings=False, up_commute=False, resample_on_load=False, fold_pose_mul=False,
+                   merge_pools=False, fuse_pool_small=False, pool_segments=False)
+    assert off.rules == RuleSet(**all_off) and on.rules == RuleSet() and off.rules != on.rules
+    # the same rules through Model.rules under a clean environment: the same plan as through the environment
+    for k in all_off:
+        monkeypatch.delenv('DEEPHAR_' + k.upper())
+    full = bench.build_speed2d()
+    by_option = Model(full.input, full.outputs[34:36])
+    by_option.rules = RuleSet(**all_off)
+    assert len(by_option.plan.steps) == 604 and by_option.plan.rules == off.rules
+    assert [(s.kind, s.name) for s in by_option.plan.steps] == [(s.kind, s.name) for s in off.steps]
+    built = by_option.plan
+    by_option.rules = RuleSet(**all_off)                  # (the same value again: no re-plan)
+    assert by_option.plan is built
+    by_option.rules = None                                # an engine option: changing it re-plans -- from the (clean) environment
+    assert by_option.plan is not built and by_option.plan.rules == RuleSet() and len(by_option.plan.steps) == 413
     _, r13 = plan(DEEPHAR_POOL_SEGMENTS='0')
     assert len(r13.steps) == 431
     # R10b: eighteen action heads, each opens with ONE 3x5 convolution of 70 columns whose parts sit centred in the window
