@@ -56,6 +56,7 @@ SIGNATURES = {
     'dh_conv2d_packed_dims': (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2),
     'dh_conv2d_pack_weights_host': (C.c_int, [vp, vp] + [C.c_int] * 4),
     'dh_conv2d_pack_weights_split_host': (C.c_int, [vp, vp] + [C.c_int] * 4),
+    'dh_conv2d_pack_weights_parts_host': (C.c_int, [vp, vp] + [C.c_int] * 5),
     'dh_conv2d_num_tile_cfgs': (C.c_int, []),
     'dh_conv2d_num_split_tile_cfgs': (C.c_int, []),
     'dh_conv2d_pick_tile_cfg': (C.c_int, [C.c_int, C.c_int]),

@@ -13,10 +13,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
-SOURCES = ["conv_igemm.hip", "gemm1x1.hip", "gemm1x1s.hip", "conv_splitk.hip", "conv_halo.hip", "conv_stem.hip", "spatial.hip", "decoder.hip",
+SOURCES = ["conv_igemm.hip", "gemm1x1.hip", "gemm1x1s.hip", "gemm1x1s_p2.hip", "gemm1x1s_p1.hip", "conv_splitk.hip", "conv_halo.hip", "conv_stem.hip", "spatial.hip", "decoder.hip",
            "capi.hip", "plan.hip"]
 HEADERS = [os.path.join(HERE, "dh_kernels.h"), os.path.join(HERE, "conv_common.h"), os.path.join(HERE, "dw_lds.h"),
            os.path.join(INCLUDE, "deephar_hip.h")]
+INCLUDES = {"gemm1x1s_p2.hip": ["gemm1x1s.hip"], "gemm1x1s_p1.hip": ["gemm1x1s.hip"]}   # sources that include a source
 LIB = os.path.join(HERE, "libdeephar_hip.so")
 OBJDIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
@@ -35,7 +36,8 @@ def _stale(target, deps):
 def _compile(src):
     obj = os.path.join(OBJDIR, src.replace(".hip", ".o"))
     path = os.path.join(HERE, src)
-    if _stale(obj, [path] + HEADERS):
+    deps = [path] + HEADERS + [os.path.join(HERE, inc) for inc in INCLUDES.get(src, [])]
+    if _stale(obj, deps):
         cmd = [HIPCC] + FLAGS + ["-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

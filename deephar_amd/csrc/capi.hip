@@ -78,27 +78,28 @@ static inline float bf16_to_f(uint16_t h) {
   return f;
 }
 
-int dh_conv2d_pack_weights_split_host(const float* w, uint16_t* packed, int KH, int KW, int Cin, int Cout) {
+int dh_conv2d_pack_weights_parts_host(const float* w, uint16_t* packed, int KH, int KW, int Cin, int Cout, int parts) {
   int Kp, Np;
-  if (w == nullptr || packed == nullptr || dh_conv2d_packed_dims(KH, KW, Cin, Cout, &Kp, &Np) != DH_OK)
+  if (w == nullptr || packed == nullptr || parts < 1 || parts > 3 || dh_conv2d_packed_dims(KH, KW, Cin, Cout, &Kp, &Np) != DH_OK)
     return DH_EINVAL;
   const int K = KH * KW * Cin;
-  memset(packed, 0, sizeof(uint16_t) * (size_t)3 * Kp * Np);
-  // unit (kg, part, n) = 8 bf16 at ((kg * 3 + part) * Np + n) * 8; element k % 8 inside
+  memset(packed, 0, sizeof(uint16_t) * (size_t)parts * Kp * Np);
+  // unit (kg, part, n) = 8 bf16 at ((kg * parts + part) * Np + n) * 8; element k % 8 inside
   for (int k = 0; k < K; ++k)
     for (int n = 0; n < Cout; ++n) {
-      const float x = w[(size_t)k * Cout + n];
-      const uint16_t h1 = bf16_rne(x);
-      const float r1 = x - bf16_to_f(h1);
-      const uint16_t h2 = bf16_rne(r1);
-      const float r2 = r1 - bf16_to_f(h2);
-      const uint16_t h3 = bf16_rne(r2);
-      const size_t base = ((size_t)(k >> 3) * 3 * Np + n) * 8 + (k & 7);
-      packed[base] = h1;
-      packed[base + (size_t)Np * 8] = h2;
-      packed[base + (size_t)2 * Np * 8] = h3;
+      float r = w[(size_t)k * Cout + n];
+      const size_t base = ((size_t)(k >> 3) * parts * Np + n) * 8 + (k & 7);
+      for (int q = 0; q < parts; ++q) {       // x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2): the residuals are exact
+        const uint16_t h = bf16_rne(r);
+        packed[base + (size_t)q * Np * 8] = h;
+        r -= bf16_to_f(h);
+      }
     }
   return DH_OK;
+}
+
+int dh_conv2d_pack_weights_split_host(const float* w, uint16_t* packed, int KH, int KW, int Cin, int Cout) {
+  return dh_conv2d_pack_weights_parts_host(w, packed, KH, KW, Cin, Cout, 3);
 }
 
 int dh_conv2d_num_tile_cfgs(void) { return conv_igemm_num_cfgs(); }

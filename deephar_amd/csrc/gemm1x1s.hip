@@ -14,6 +14,11 @@
 // (profiles/parity_r02_bf16x3.json); they are NOT bit-identical to the fp32-MFMA path, which remains the default.
 // Weights are split once on the host (dh_conv2d_pack_weights_split_host / engine/packing.py):
 //   [K/8][3 parts][Np][8 bf16]  -- one 16-byte unit per (k-group, part, column) = one lane's B operand.
+// The same kernel with P = 2 or 1 parts per operand is the reduced-precision ladder below bf16x3 (dh_conv_args.w_split = 3 / 4,
+// Model.gemm_precision = 'bf16x2' / 'bf16'): the products with (a part) + (b part) <= P + 1 -- a2 b1, a1 b2, a1 b1 (about 2^-16
+// per product) or a1 b1 alone (plain bf16 operands, about 2^-8) -- i.e. 3 or 1 MFMA per 16 k instead of 6, one or no
+// residual pass in the activation split, a B stage of 4 P BN units, weights packed [K/8][P parts][Np][8].  Same K order,
+// same epilogue, bit-identical across tilings within a mode; the wide tiling below exists for P = 3 only.
 // Reference layers replaced: as gemm1x1.hip (deephar/layers.py:74-80, 258-301; models/reception.py:43-98).
 #include "conv_common.h"
 
@@ -73,11 +78,17 @@ __device__ __forceinline__ unsigned pack_pair(float x0, float x1) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 
-struct Frag3 { bf16x8 p[3]; };
+// P = number of bf16 parts kept per operand (3: "bf16x3", 2: "bf16x2", 1: plain "bf16"); the products kept are those
+// with (a part) + (b part) <= P + 1 (1-based): 6, 3, 1 of them
+template <int P> struct Frag { bf16x8 p[P]; };
+typedef Frag<3> Frag3;
+constexpr int nprod(int P) { return P * (P + 1) / 2; }
+constexpr int split_valu(int P) { return P == 3 ? 52 : (P == 2 ? 32 : 12); }   // VALU instructions of one split8 (8 of them the ReLU)
 
-// 8 consecutive k of one row (two float4) -> three bf16x8 operands
-template <bool RELU>
-__device__ __forceinline__ Frag3 split8(float4 lo4, float4 hi4) {
+// 8 consecutive k of one row (two float4) -> P bf16x8 operands: P - 1 residual passes, the last part is one
+// v_cvt_pk_bf16_f32 per pair
+template <bool RELU, int P = 3>
+__device__ __forceinline__ Frag<P> split8(float4 lo4, float4 hi4) {
   float x[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
   if constexpr (RELU) {
 #pragma unroll
@@ -85,16 +96,20 @@ __device__ __forceinline__ Frag3 split8(float4 lo4, float4 hi4) {
   }
   unsigned a[4], b[4], c[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) a[i] = split_pair(x[2 * i], x[2 * i + 1]);
+  for (int i = 0; i < 4; ++i) a[i] = P > 1 ? split_pair(x[2 * i], x[2 * i + 1]) : pack_pair(x[2 * i], x[2 * i + 1]);
+  if constexpr (P > 1) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) b[i] = split_pair(x[2 * i], x[2 * i + 1]);
+    for (int i = 0; i < 4; ++i) b[i] = P > 2 ? split_pair(x[2 * i], x[2 * i + 1]) : pack_pair(x[2 * i], x[2 * i + 1]);
+  }
+  if constexpr (P > 2) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = pack_pair(x[2 * i], x[2 * i + 1]);
-  Frag3 f;
+    for (int i = 0; i < 4; ++i) c[i] = pack_pair(x[2 * i], x[2 * i + 1]);
+  }
+  Frag<P> f;
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   f.p[0] = __builtin_bit_cast(bf16x8, (u32x4){a[0], a[1], a[2], a[3]});
-  f.p[1] = __builtin_bit_cast(bf16x8, (u32x4){b[0], b[1], b[2], b[3]});
-  f.p[2] = __builtin_bit_cast(bf16x8, (u32x4){c[0], c[1], c[2], c[3]});
+  if constexpr (P > 1) f.p[1] = __builtin_bit_cast(bf16x8, (u32x4){b[0], b[1], b[2], b[3]});
+  if constexpr (P > 2) f.p[2] = __builtin_bit_cast(bf16x8, (u32x4){c[0], c[1], c[2], c[3]});
   return f;
 }
 
@@ -108,24 +123,14 @@ __device__ __forceinline__ bf16x8 as_bf(float4 v) {
 // tile-major (six dependent MFMAs on one accumulator back to back) every MFMA waits out its predecessor's result
 // latency, which is longer than the 32-cycle issue interval of v_mfma_f32_32x32x16_bf16 (measured: matrix pipe 42 % busy,
 // 56 % of the wave cycles in issue stalls).  The order per accumulator -- and with it every result bit -- is unchanged.
-template <int TM, int TN>
-__device__ __forceinline__ void mfma6_tiles(const Frag3 (&a)[TM], const bf16x8 (&b)[TN][3], f32x16 (&acc)[TM][TN]) {
+// With P parts the list is its tail: P = 2 keeps (1,0) (0,1) (0,0), P = 1 keeps (0,0) -- still smallest first.
+// products [T0, T1) of the P-part sequence, T1 <= nprod(P)
+template <int TM, int TN, int T0, int T1, int P = 3>
+__device__ __forceinline__ void mfma_products(const Frag<P> (&a)[TM], const bf16x8 (&b)[TN][P], f32x16 (&acc)[TM][TN]) {
   constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+  static_assert(T1 <= nprod(P), "product list");
 #pragma unroll
-  for (int t = 0; t < 6; ++t)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i].p[PA[t]], b[j][PB[t]], acc[i][j], 0, 0, 0);
-}
-
-// products [T0, T1) of the same sequence
-template <int TM, int TN, int T0, int T1>
-__device__ __forceinline__ void mfma_products(const Frag3 (&a)[TM], const bf16x8 (&b)[TN][3], f32x16 (&acc)[TM][TN]) {
-  constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-  for (int t = T0; t < T1; ++t)
+  for (int t = T0 + 6 - nprod(P); t < T1 + 6 - nprod(P); ++t)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -135,17 +140,19 @@ __device__ __forceinline__ void mfma_products(const Frag3 (&a)[TM], const bf16x8
 
 // NS = number of LDS stages: 2 (next K-step in flight) or 3 (two K-steps in flight: the split kernel's K-step is short
 // enough that one DMA round trip no longer fits under it).
-template <int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, int NS = 2>
+// P = bf16 parts per operand: the ninth template argument (a profiler spells the three-part kernels <..., 3>)
+template <int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, int NS = 2, int P = 3>
 __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_kernel(const ConvArgs p, const int epi_vec) {
   constexpr int NT = WM * WN * 64;
   constexpr bool PIPELINED = TM == 1;                    // software-pipelined K loop (below); else one chunk at a time
   constexpr int BM = WM * TM * 32;
   constexpr int BN = WN * TN * 32;
   constexpr int APASS = BM * 8 / NT;
-  constexpr int BPASS = (12 * BN + NT - 1) / NT;         // 16-byte units per thread: 4 k-groups x 3 parts x BN
-  constexpr int BROWS = 12 * BN;                         // 16-byte units of the B stage (the last pass is partial)
+  constexpr int BROWS = 4 * P * BN;                      // 16-byte units of the B stage: 4 k-groups x P parts x BN
+  constexpr int BPASS = (BROWS + NT - 1) / NT;           // 16-byte units per thread (the last pass is partial)
   constexpr int STAGE = BM * BK + BROWS * 4;             // floats per stage
-  static_assert(BM * 8 % NT == 0 && (12 * BN) % 64 == 0, "tile/thread mismatch");
+  constexpr int NPROD = nprod(P);
+  static_assert(BM * 8 % NT == 0 && BROWS % 64 == 0, "tile/thread mismatch");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -165,8 +172,8 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.x), 0, (int)(((unsigned)(p.N * p.H * p.W - 1) * p.ldx + (unsigned)p.Cin) * 4u), 0x00020000);
-  const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, (int)((unsigned)p.Kp * p.Np * 6u),
-                                                      0x00020000);
+  const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0,
+                                                      (int)((unsigned)p.Kp * p.Np * (2u * P)), 0x00020000);
   unsigned a_off[APASS];                                  // pointwise: (pixel * ldx + slot) * 4, fixed over K
   int a_slot[APASS];
   int a_pix[KXK ? APASS : 1], a_ih0[KXK ? APASS : 1], a_iw0[KXK ? APASS : 1];
@@ -189,16 +196,16 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
     }
   }
   const int chunks_per_tap = KXK ? p.Cin / BK : 1;
-  // packed split weight: 16-byte unit (kg, part, n) at ((kg * 3 + part) * Np + n) * 16 bytes
+  // packed split weight: 16-byte unit (kg, part, n) at ((kg * P + part) * Np + n) * 16 bytes
   unsigned b_off[BPASS];
 #pragma unroll
   for (int q = 0; q < BPASS; ++q) {
     const int idx = tid + q * NT;
     const int r = idx / BN;
     const int j = idx - r * BN;
-    b_off[q] = r < 12 && n0 + j < p.Np ? ((unsigned)r * p.Np + n0 + j) * 16u : OOB;
+    b_off[q] = r < 4 * P && n0 + j < p.Np ? ((unsigned)r * p.Np + n0 + j) * 16u : OOB;
   }
-  const int b_step = 12 * p.Np * 16;                      // bytes per K-step in the packed weight
+  const int b_step = 4 * P * p.Np * 16;                     // bytes per K-step in the packed weight
 
   auto issue = [&](int kt, int stage) {
     float* sA = smem + stage * STAGE;
@@ -223,7 +230,7 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
     }
 #pragma unroll
     for (int q = 0; q < BPASS; ++q)
-      if ((q + 1) * NT <= BROWS || q * NT + wave_u * 64 < BROWS)     // whole waves: 12 * BN is a multiple of 64
+      if ((q + 1) * NT <= BROWS || q * NT + wave_u * 64 < BROWS)     // whole waves: BROWS is a multiple of 64
         dma16(rs_w, sB + (q * NT + wave_u * 64) * 4, b_off[q], kt * b_step);
   };
 
@@ -277,8 +284,8 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
       for (int h = 0; h < 2; ++h)
         a_base[c][i][h] = lds0 + (unsigned)(((wm * TM + i) * 32 + li) * BK * 4 +
                                             (((2 * (2 * c + lh) + h) ^ (li & 7)) << 4));
-  // B: unit ((2c + lh) * 3 + part) * BN + column
-  const unsigned b_base = lds0 + (unsigned)(BM * BK * 4) + (unsigned)((lh * 3 * BN + wn * TN * 32 + li) * 16);
+  // B: unit ((2c + lh) * P + part) * BN + column
+  const unsigned b_base = lds0 + (unsigned)(BM * BK * 4) + (unsigned)((lh * P * BN + wn * TN * 32 + li) * 16);
 
   EpiPrefetch<TM, TN> pre;
   if constexpr (!PIPELINED) {
@@ -297,7 +304,7 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
       // operands at a time -- no operand double buffering, the partner wave of the SIMD covers the read latency
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        float4 ra1[TM][2], rb1[TN][3];
+        float4 ra1[TM][2], rb1[TN][P];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           ra1[i][0] = lds_rd<0>(a_base[c][i][0] + so);
@@ -305,22 +312,22 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          rb1[j][0] = lds_rd<0>(bo + (unsigned)((6 * c) * BN * 16 + j * 512));
-          rb1[j][1] = lds_rd<0>(bo + (unsigned)((6 * c + 1) * BN * 16 + j * 512));
-          rb1[j][2] = lds_rd<0>(bo + (unsigned)((6 * c + 2) * BN * 16 + j * 512));
+          rb1[j][0] = lds_rd<0>(bo + (unsigned)((2 * P * c) * BN * 16 + j * 512));
+          if constexpr (P > 1) rb1[j][1] = lds_rd<0>(bo + (unsigned)((2 * P * c + 1) * BN * 16 + j * 512));
+          if constexpr (P > 2) rb1[j][2] = lds_rd<0>(bo + (unsigned)((2 * P * c + 2) * BN * 16 + j * 512));
         }
         __builtin_amdgcn_sched_barrier(0);
         if (c == 0 && more) issue(kt + NS - 1, nxt);
         lgkm_wait();
-        Frag3 fa[TM];
+        Frag<P> fa[TM];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) fa[i] = split8<RELU>(ra1[i][0], ra1[i][1]);
-        bf16x8 fb[TN][3];
+        for (int i = 0; i < TM; ++i) fa[i] = split8<RELU, P>(ra1[i][0], ra1[i][1]);
+        bf16x8 fb[TN][P];
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-          for (int q = 0; q < 3; ++q) fb[j][q] = as_bf(rb1[j][q]);
-        mfma6_tiles<TM, TN>(fa, fb, acc);
+          for (int q = 0; q < P; ++q) fb[j][q] = as_bf(rb1[j][q]);
+        mfma_products<TM, TN, 0, NPROD, P>(fa, fb, acc);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -348,7 +355,7 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
   // SIMD fall into step: the pipe is shared while both multiply and idle while both fetch).
   // One barrier per K-step, at the top of its SECOND chunk: by then every wave has finished reading stage kt-1 ... so
   // the DMA of K-step kt+NS-1 may overwrite it, and K-step kt+1 (issued NS-1 K-steps earlier) has landed.
-  struct Ops { Frag3 a[TM]; bf16x8 b[TN][3]; };
+  struct Ops { Frag<P> a[TM]; bf16x8 b[TN][P]; };
   Ops o0, o1;
   float4 ra[TM][2];
   auto read_chunk = [&](Ops& o, const unsigned (&ab)[TM][2], unsigned so, unsigned boff) {
@@ -360,31 +367,31 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) o.b[j][q] = as_bf(lds_rd<0>(b_base + so + boff + (unsigned)(q * BN * 16 + j * 512)));
+      for (int q = 0; q < P; ++q) o.b[j][q] = as_bf(lds_rd<0>(b_base + so + boff + (unsigned)(q * BN * 16 + j * 512)));
   };
-  constexpr int NPRE = 2;                                  // products issued before the wait for the next operands
-  constexpr int VPM = (52 * TM + (6 - NPRE) * TM * TN - 1) / ((6 - NPRE) * TM * TN);
+  constexpr int NPRE = P == 3 ? 2 : P - 1;                 // products issued before the wait for the next operands
+  constexpr int VPM = (split_valu(P) * TM + (NPROD - NPRE) * TM * TN - 1) / ((NPROD - NPRE) * TM * TN);
   // multiply `cur`; when `fetch`, the reads for `nxt` are already in flight: wait for them after NPRE products and
   // split the A rows under the remaining MFMAs (VPM VALU instructions behind each; about four hide, measured)
   auto multiply = [&](const Ops& cur, Ops& nxt, bool fetch) {
     __builtin_amdgcn_sched_barrier(0);
-    mfma_products<TM, TN, 0, NPRE>(cur.a, cur.b, acc);
+    mfma_products<TM, TN, 0, NPRE, P>(cur.a, cur.b, acc);
     if (fetch) {
       lgkm_wait();
 #pragma unroll
-      for (int i = 0; i < TM; ++i) nxt.a[i] = split8<RELU>(ra[i][0], ra[i][1]);
-      mfma_products<TM, TN, NPRE, 6>(cur.a, cur.b, acc);
+      for (int i = 0; i < TM; ++i) nxt.a[i] = split8<RELU, P>(ra[i][0], ra[i][1]);
+      mfma_products<TM, TN, NPRE, NPROD, P>(cur.a, cur.b, acc);
 #pragma unroll
       for (int i = 0; i < TM; ++i)                              // keep the split HERE (it would be sunk to its first use)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) asm volatile("" : "+v"(nxt.a[i].p[q]));
+        for (int q = 0; q < P; ++q) asm volatile("" : "+v"(nxt.a[i].p[q]));
 #pragma unroll
-      for (int u = 0; u < (6 - NPRE) * TM * TN; ++u) {
+      for (int u = 0; u < (NPROD - NPRE) * TM * TN; ++u) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
         __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);    // VPM VALU
       }
     } else {
-      mfma_products<TM, TN, NPRE, 6>(cur.a, cur.b, acc);
+      mfma_products<TM, TN, NPRE, NPROD, P>(cur.a, cur.b, acc);
     }
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -393,13 +400,13 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
   read_chunk(o0, a_base[0], 0u, 0u);
   lgkm_wait();
 #pragma unroll
-  for (int i = 0; i < TM; ++i) o0.a[i] = split8<RELU>(ra[i][0], ra[i][1]);
+  for (int i = 0; i < TM; ++i) o0.a[i] = split8<RELU, P>(ra[i][0], ra[i][1]);
 
   int cur = 0;
   for (int kt = 0; kt < nk - 1; ++kt) {               // the last K-step is peeled: no branch around the MFMA streams
     const unsigned so = (unsigned)(cur * STAGE * 4);
     // first chunk of the K-step: fetch its second one
-    read_chunk(o1, a_base[1], so, (unsigned)(6 * BN * 16));
+    read_chunk(o1, a_base[1], so, (unsigned)(2 * P * BN * 16));
     multiply(o0, o1, true);
     // second chunk: open K-step kt+1
     const int nst = cur + 1 == NS ? 0 : cur + 1;
@@ -411,7 +418,7 @@ __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_ke
     cur = nst;
   }
   pre.template issue<WM, WN>(p, m0, n0, M, epi_vec);
-  read_chunk(o1, a_base[1], (unsigned)(cur * STAGE * 4), (unsigned)(6 * BN * 16));
+  read_chunk(o1, a_base[1], (unsigned)(cur * STAGE * 4), (unsigned)(2 * P * BN * 16));
   multiply(o0, o1, true);
   multiply(o1, o0, false);
   }
@@ -665,14 +672,13 @@ int launch_wide(const ConvArgs& a, int epi, hipStream_t s) {
                     : launch_wide_variant<WM, false, false, false>(a, epi, t, s);
 }
 
-template <int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, int NS = 2>
+template <int P, int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, int NS = 2>
 int launch_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  constexpr int BPASS = (12 * BN + NT - 1) / NT;
-  constexpr int kStage = NS * (BM * BK + 12 * BN * 4), kEpi = WM * WN * 32 * (TN * 32 + 4);
+  constexpr int kStage = NS * (BM * BK + 4 * P * BN * 4), kEpi = WM * WN * 32 * (TN * 32 + 4);
   constexpr size_t lds = (size_t)(kStage > kEpi ? kStage : kEpi) * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  auto kern = gemm1x1s_kernel<WM, WN, TM, TN, UP2, RELU, KXK, NS>;
+  auto kern = gemm1x1s_kernel<WM, WN, TM, TN, UP2, RELU, KXK, NS, P>;
   if (lds > 64 * 1024) {
     static LdsLimit lim;
     lim.raise((const void*)kern, (int)lds);
@@ -681,7 +687,7 @@ int launch_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t s) {
   return check_launch();
 }
 
-template <int WM, int WN, int TM, int TN, int NS = 2>
+template <int P, int WM, int WN, int TM, int TN, int NS = 2>
 int launch_cfg(const ConvArgs& a, int epi, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const long long M = (long long)a.N * a.OH * a.OW;
@@ -693,22 +699,66 @@ int launch_cfg(const ConvArgs& a, int epi, hipStream_t s) {
     if constexpr (TM * TN >= 6) {
       return DH_EUNSUPPORTED;
     } else {
-      return a.pre_relu ? launch_variant<WM, WN, TM, TN, true, true, false, NS>(a, epi, t, s)
-                        : launch_variant<WM, WN, TM, TN, true, false, false, NS>(a, epi, t, s);
+      return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, true, true, false, NS>(a, epi, t, s)
+                        : launch_variant<P, WM, WN, TM, TN, true, false, false, NS>(a, epi, t, s);
     }
   }
   if (!(a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PT == 0 && a.PL == 0))
-    return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true, true, NS>(a, epi, t, s)
-                      : launch_variant<WM, WN, TM, TN, false, false, true, NS>(a, epi, t, s);
-  return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true, false, NS>(a, epi, t, s)
-                    : launch_variant<WM, WN, TM, TN, false, false, false, NS>(a, epi, t, s);
+    return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, false, true, true, NS>(a, epi, t, s)
+                      : launch_variant<P, WM, WN, TM, TN, false, false, true, NS>(a, epi, t, s);
+  return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, false, true, false, NS>(a, epi, t, s)
+                    : launch_variant<P, WM, WN, TM, TN, false, false, false, NS>(a, epi, t, s);
+}
+
+// every tiling of one mode (P parts).  The wide tiling exists for three parts only: with fewer products per K-step its
+// fixed half-tile choreography has nothing left to hide the operand traffic under.
+template <int P>
+int launch_split_parts(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
+  switch (cfg) {
+    case 0: return launch_cfg<P, 2, 2, 2, 3>(a, epi, s);
+    case 1: return launch_cfg<P, 2, 2, 2, 2>(a, epi, s);
+    case 2: return launch_cfg<P, 4, 1, 1, 3>(a, epi, s);
+    case 3: return launch_cfg<P, 4, 1, 1, 2>(a, epi, s);
+    case 4: return launch_cfg<P, 4, 1, 1, 1>(a, epi, s);
+    case 5: return launch_cfg<P, 2, 1, 1, 3>(a, epi, s);
+    case 6: return launch_cfg<P, 2, 1, 1, 2>(a, epi, s);
+    case 7: return launch_cfg<P, 2, 1, 1, 1>(a, epi, s);
+    case 8: return launch_cfg<P, 1, 1, 1, 1>(a, epi, s);
+    // one work-group per CU, three LDS stages: two K-steps of DMA in flight, bigger tiles = less L2 -> LDS traffic per MAC
+    case 9: return launch_cfg<P, 8, 1, 1, 3, 3>(a, epi, s);      // 256 x 96, 8 waves
+    case 10: return launch_cfg<P, 4, 1, 1, 3, 3>(a, epi, s);     // 128 x 96, 4 waves
+    case 11: return launch_cfg<P, 8, 1, 1, 2, 3>(a, epi, s);     // 256 x 64
+    case 12: return launch_cfg<P, 4, 2, 1, 3, 2>(a, epi, s);     // 128 x 192, 8 waves, two stages
+    case 13: return launch_cfg<P, 4, 2, 2, 3, 2>(a, epi, s);     // 256 x 192, 8 waves of 64 x 96
+    case 14:                                                     // 128 x 192, 4 waves of 32 x 192, 16-k K-steps
+      if constexpr (P == 3) return launch_wide<4>(a, epi, s);
+      else return DH_EUNSUPPORTED;
+    case 15:                                                     // 64 x 192
+      if constexpr (P == 3) return launch_wide<2>(a, epi, s);
+      else return DH_EUNSUPPORTED;
+  }
+  return DH_EINVAL;
 }
 
 }  // namespace
 
-bool gemm1x1_eligible(const ConvArgs& a);
+// One translation unit per mode (the instantiations of a mode compile for about as long as the rest of the library):
+// this file is the three-part mode and the dispatch, gemm1x1s_p2.hip / gemm1x1s_p1.hip include it with DH_SPLIT_PARTS set.
+#ifndef DH_SPLIT_PARTS
+#define DH_SPLIT_PARTS 3
+#endif
 
-// What dh_conv2d_f32 accepts with w_split = 1 (the weight pointer itself is not looked at: a binding asks before it packs).
+#if DH_SPLIT_PARTS == 2
+int launch_gemm1x1_split_p2(const ConvArgs& a, int cfg, int epi, hipStream_t s) { return launch_split_parts<2>(a, cfg, epi, s); }
+#elif DH_SPLIT_PARTS == 1
+int launch_gemm1x1_split_p1(const ConvArgs& a, int cfg, int epi, hipStream_t s) { return launch_split_parts<1>(a, cfg, epi, s); }
+#else
+bool gemm1x1_eligible(const ConvArgs& a);
+int launch_gemm1x1_split_p2(const ConvArgs& a, int cfg, int epi, hipStream_t s);
+int launch_gemm1x1_split_p1(const ConvArgs& a, int cfg, int epi, hipStream_t s);
+
+// What dh_conv2d_f32 accepts with a split packing, w_split = 1 / 3 / 4: one rule for every mode (the weight pointer itself
+// is not looked at: a binding asks before it packs).
 bool gemm1x1_split_eligible(const ConvArgs& a0) {
   ConvArgs a = a0;
   a.w = reinterpret_cast<const float*>(uintptr_t(16));
@@ -718,30 +768,20 @@ bool gemm1x1_split_eligible(const ConvArgs& a0) {
   return (long long)a.N * a.H * a.W * a.ldx * 4 <= 0xf0000000LL && (long long)a.Kp * a.Np * 6 <= 0xf0000000LL;
 }
 
+// bf16 parts per operand of a split packing (dh_conv_args.w_split), 0 for the fp32 packings
+int conv_split_parts(int w_split) { return w_split == 1 ? 3 : (w_split == 3 ? 2 : (w_split == 4 ? 1 : 0)); }
+
 int launch_gemm1x1_split(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
   if (!gemm1x1_eligible(a) || !gemm1x1_split_eligible(a)) return DH_EUNSUPPORTED;
-  switch (cfg) {
-    case 0: return launch_cfg<2, 2, 2, 3>(a, epi, s);
-    case 1: return launch_cfg<2, 2, 2, 2>(a, epi, s);
-    case 2: return launch_cfg<4, 1, 1, 3>(a, epi, s);
-    case 3: return launch_cfg<4, 1, 1, 2>(a, epi, s);
-    case 4: return launch_cfg<4, 1, 1, 1>(a, epi, s);
-    case 5: return launch_cfg<2, 1, 1, 3>(a, epi, s);
-    case 6: return launch_cfg<2, 1, 1, 2>(a, epi, s);
-    case 7: return launch_cfg<2, 1, 1, 1>(a, epi, s);
-    case 8: return launch_cfg<1, 1, 1, 1>(a, epi, s);
-    // one work-group per CU, three LDS stages: two K-steps of DMA in flight, bigger tiles = less L2 -> LDS traffic per MAC
-    case 9: return launch_cfg<8, 1, 1, 3, 3>(a, epi, s);      // 256 x 96, 8 waves
-    case 10: return launch_cfg<4, 1, 1, 3, 3>(a, epi, s);     // 128 x 96, 4 waves
-    case 11: return launch_cfg<8, 1, 1, 2, 3>(a, epi, s);     // 256 x 64
-    case 12: return launch_cfg<4, 2, 1, 3, 2>(a, epi, s);     // 128 x 192, 8 waves, two stages
-    case 13: return launch_cfg<4, 2, 2, 3, 2>(a, epi, s);     // 256 x 192, 8 waves of 64 x 96
-    case 14: return launch_wide<4>(a, epi, s);                // 128 x 192, 4 waves of 32 x 192, 16-k K-steps
-    case 15: return launch_wide<2>(a, epi, s);                // 64 x 192
+  switch (conv_split_parts(a.w_split)) {
+    case 3: return launch_split_parts<3>(a, cfg, epi, s);
+    case 2: return launch_gemm1x1_split_p2(a, cfg, epi, s);
+    case 1: return launch_gemm1x1_split_p1(a, cfg, epi, s);
   }
   return DH_EINVAL;
 }
 
 int gemm1x1_split_num_cfgs() { return 16; }
+#endif
 
 }  // namespace dh

@@ -6,12 +6,15 @@ torch compute and no CPU fallback.  The launch sequence of a bound plan is captu
 (dh_graph_*), so steady-state `predict` costs one graph launch per batch instead of ~300 kernel launches.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 
 from .. import _lib
 from . import packing
+
+SPLIT_CODES = {'bf16x3': 1, 'bf16x2': 3, 'bf16': 4}      # Plan.gemm_precision -> dh_conv_args.w_split (packing.SPLIT_PARTS)
 
 BN_EPS = 1e-3  # keras BatchNormalization default epsilon (SURVEY.md A.3)
 
@@ -43,12 +46,14 @@ class WeightStore:
         return p.value
 
     def conv_weight(self, p, split=0):
-        """split = dh_conv_args.w_split: 0 fp32 tap-major, 1 the split-bf16 packing, 2 fp32 chunk-major (halo-resident
-        K x K kernel); different packings of one Param are kept side by side when several are in use."""
+        """split = dh_conv_args.w_split: 0 fp32 tap-major, 1 / 3 / 4 the split-bf16 packing with three / two / one part,
+        2 fp32 chunk-major (halo-resident K x K kernel); different packings of one Param are kept side by side when
+        several are in use."""
         key = (id(p), int(split))
         ent = self.conv.get(key)
         if ent is None or ent[3] != p.version:
-            packer = {0: packing.pack_conv, 1: packing.pack_conv_split, 2: packing.pack_conv_halo}[int(split)]
+            packer = {0: packing.pack_conv, 2: packing.pack_conv_halo}.get(int(split)) or \
+                functools.partial(packing.pack_conv_split, parts=packing.SPLIT_PARTS[int(split)])
             packed, kp, np_ = packer(self._require(p))
             if ent is None:
                 ent = (self._dev(packed), kp, np_, p.version)
@@ -201,12 +206,13 @@ class BoundPlan:
         self.absorbed = {}        # index of a grouped / paired launch -> the Step whose work it also does
 
     def weight_layout(self, args):
-        """dh_conv_args.w_split of a conv step: 1 = split-bf16 (plan.gemm_precision == 'bf16x3' and the library takes the
-        layer: dh_conv2d_split_eligible), 2 = fp32 chunk-major for the halo-resident K x K kernel
+        """dh_conv_args.w_split of a conv step: 1 / 3 / 4 = split-bf16 (plan.gemm_precision == 'bf16x3' / 'bf16x2' / 'bf16'
+        and the library takes the layer: dh_conv2d_split_eligible, one rule for the three), 2 = fp32 chunk-major for the halo-resident K x K kernel
         (dh_conv2d_halo_eligible: a rule on the per-frame geometry), else 0.  The LIBRARY decides, asked with the launch's
         own argument struct before the weights are packed -- a layer is never bound with a packing its launch rejects."""
-        if getattr(self.plan, 'gemm_precision', 'f32') == 'bf16x3' and self.lib.dh_conv2d_split_eligible(C.byref(args)):
-            return 1
+        code = SPLIT_CODES.get(getattr(self.plan, 'gemm_precision', 'f32'))
+        if code and self.lib.dh_conv2d_split_eligible(C.byref(args)):
+            return code
         if self.plan.rules.halo_conv and self.lib.dh_conv2d_halo_eligible(C.byref(args)):
             return 2
         return 0
@@ -676,7 +682,7 @@ class BoundPlan:
             ncfg = ncfgs[step.kind]
             cargs = args[0]._obj
             sig = (self.n, step.kind) + self._conv_signature(step) + ((('u8',) if cargs.x_u8 else ())) + \
-                ((({1: 'bf16x3', 2: 'halo'}[cargs.w_split],) if cargs.w_split else ()))
+                ((({1: 'bf16x3', 2: 'halo', 3: 'bf16x2', 4: 'bf16'}[cargs.w_split],) if cargs.w_split else ()))
             if cargs.w_split:
                 ncfg = lib.dh_conv2d_num_halo_tile_cfgs() if cargs.w_split == 2 else lib.dh_conv2d_num_split_tile_cfgs()
             if step.kind == 'conv' and lib.dh_conv2d_uses_split_k(args[0]):

@@ -189,7 +189,7 @@ class Plan:
         self.out_items = 0     # the model outputs occupy [0, out_items) of it (schedule.allocate)
         self.params = []       # ordered unique graph.Param list
         self.nstreams = 1
-        self.gemm_precision = 'f32'   # 'bf16x3': eligible convs run split-bf16 on the bf16 matrix cores (executor)
+        self.gemm_precision = 'f32'   # 'bf16x3' / 'bf16x2' / 'bf16': eligible convs run split-bf16 on the bf16 matrix cores (executor)
         self.rules = RuleSet()        # the rule switches the plan was built under (build_plan: read once, recorded here)
 
     @property
@@ -1450,11 +1450,14 @@ class Planner:
         self.plan.params = out
 
 
+GEMM_PRECISIONS = ('f32', 'bf16x3', 'bf16x2', 'bf16')    # Plan.gemm_precision: the executor maps it to dh_conv_args.w_split
+
+
 def build_plan(inputs, outputs, nstreams=1, gemm_precision='f32', stream_policy='list', rules=None):
     """rules: the RuleSet the plan is built and later bound under; None = RuleSet.from_env(), read here, once."""
     rules = RuleSet.from_env() if rules is None else rules
-    if gemm_precision not in ('f32', 'bf16x3'):
-        raise ValueError("gemm_precision must be 'f32' or 'bf16x3', got %r" % (gemm_precision,))
+    if gemm_precision not in GEMM_PRECISIONS:
+        raise ValueError("gemm_precision must be one of %s, got %r" % ('/'.join(map(repr, GEMM_PRECISIONS)), gemm_precision))
     if stream_policy not in ('list', 'tail'):
         raise ValueError("stream_policy must be 'list' or 'tail', got %r" % (stream_policy,))
     plan = Planner(inputs, outputs, nstreams, stream_policy, rules).run()

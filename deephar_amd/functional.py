@@ -45,9 +45,13 @@ def pack_conv_weight(w_hwio, device='cuda'):
 
 def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=None, pre_relu=False,
            post_scale=None, post_shift=None, post_relu=False, res1=None, res2=None, up2=False, tile_cfg=-1,
-           packed=None, in_lut=None, split=False, halo=False, res2_down=False, pool2=False, x_resample=0, seg=None):
+           packed=None, in_lut=None, split=False, halo=False, res2_down=False, pool2=False, x_resample=0, seg=None,
+           precision=None):
     """Fused conv (see dh_conv2d_f32).  x [N,H,W,Cin]; w_hwio numpy [kh,kw,Cin,Cout].  A uint8 `x` needs
-    `in_lut` (float32 [Cin,256] device tensor, engine.executor.normalization_lut): bytes are normalised on load."""
+    `in_lut` (float32 [Cin,256] device tensor, engine.executor.normalization_lut): bytes are normalised on load.
+    precision: None / 'f32' (fp32 matrix path), or 'bf16x3' / 'bf16x2' / 'bf16' -- the split-bf16 GEMM with three / two / one
+    bf16 part per operand (dh_conv_args.w_split = 1 / 3 / 4); split=True means 'bf16x3'.  A `packed` weight must have been
+    packed for the same mode."""
     torch = _t()
     if x.dtype == torch.uint8:
         if in_lut is None or tuple(in_lut.shape) != (x.shape[-1], 256):
@@ -75,8 +79,15 @@ def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=
     else:
         pt = pl = 0
         oh, ow = (h - kh) // strides[0] + 1, (w_ - kw) // strides[1] + 1
-    if split and packed is None:
-        pk, kp, np_ = packing.pack_conv_split(np.asarray(w_hwio, np.float32))
+    if precision not in (None, 'f32', 'bf16x3', 'bf16x2', 'bf16'):
+        raise ValueError("precision must be 'f32', 'bf16x3', 'bf16x2' or 'bf16', got %r" % (precision,))
+    if split and precision not in (None, 'bf16x3'):
+        raise ValueError("split=True means precision='bf16x3', got precision=%r" % (precision,))
+    if halo and precision not in (None, 'f32'):
+        raise ValueError('the halo-resident kernel takes fp32 weights only')
+    w_split = {None: int(bool(split)), 'f32': 0, 'bf16x3': 1, 'bf16x2': 3, 'bf16': 4}[precision]
+    if w_split and packed is None:
+        pk, kp, np_ = packing.pack_conv_split(np.asarray(w_hwio, np.float32), parts=packing.SPLIT_PARTS[w_split])
         packed = (torch.from_numpy(pk).to(x.device), kp, np_)
     if halo and packed is None:                  # chunk-major fp32 packing for the halo-resident K x K kernel
         pk, kp, np_ = packing.pack_conv_halo(np.asarray(w_hwio, np.float32))
@@ -85,7 +96,7 @@ def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=
     up = 2 if up2 else 1
     y = torch.empty((n, oh * up, ow * up, cout), dtype=torch.float32, device=x.device)
     a = _lib.ConvArgs()
-    a.w_split = 2 if halo else int(split)
+    a.w_split = 2 if halo else w_split
     a.x, a.w, a.y = _p(x), _p(wt), _p(y)
     a.pre_scale, a.pre_shift, a.post_scale, a.post_shift = _p(pre_scale), _p(pre_shift), _p(post_scale), _p(post_shift)
     a.res1, a.res2 = _p(res1), _p(res2)

@@ -22,7 +22,7 @@ class CallRec:
         self.model, self.inputs, self.outputs = model, list(inputs), list(outputs)
 
 
-_ENGINE_CHOICES = {'stream_policy': ('list', 'tail'), 'gemm_precision': ('f32', 'bf16x3')}
+_ENGINE_CHOICES = {'stream_policy': ('list', 'tail'), 'gemm_precision': ('f32', 'bf16x3', 'bf16x2', 'bf16')}
 
 
 class Model:
@@ -53,7 +53,10 @@ class Model:
         self.channel_power = 1
         # 'f32' (default): every conv on the fp32 matrix path, an exact k-ordered fmaf chain.  'bf16x3': pointwise / K x K
         # GEMM-shaped convs split their fp32 operands exactly into three bf16 parts and run six partial products on the
-        # bf16 matrix cores with fp32 accumulation (csrc/gemm1x1s.hip): same accuracy class, ~1.7x faster, not bit-identical
+        # bf16 matrix cores with fp32 accumulation (csrc/gemm1x1s.hip): same accuracy class, ~1.7x faster, not bit-identical.
+        # 'bf16x2' / 'bf16': the reduced-precision rungs of the same family -- two parts and three products (~2^-16 per
+        # product) or one part and one product (~2^-8, plain bf16 operands); the same layers, the same fp32 accumulation and
+        # epilogue, NOT the 1e-3 px class (README "GEMM precision ladder", tests/test_gpu_bf16_modes.py)
         self.gemm_precision = __import__('os').environ.get('DEEPHAR_GEMM', 'f32')
         # the engine's rule switches (engine/rules.py: RuleSet) the plan is built and bound under; None: read from the
         # environment when the plan is built (RuleSet.from_env).  The plan records them either way: self.plan.rules

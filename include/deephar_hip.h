@@ -72,12 +72,18 @@ typedef struct dh_conv_args {
                    (dh_conv2d_uses_first_layer_kernel) take it */
   int32_t w_split; /* weight layout.  0: fp32, [Kp/4][Np][4], K tap-major.  2: fp32, same container, K chunk-major for the
                       halo-resident K x K kernel (see dh_conv2d_halo_eligible).
-                      1: `w` was packed by dh_conv2d_pack_weights_split_host (every weight split exactly into three bf16
+                      1 ("bf16x3"): `w` was packed by dh_conv2d_pack_weights_split_host (every weight split exactly into three bf16
                       parts) and the convolution runs on the bf16 matrix cores: fp32 activations are split the same way
                       on the fly, six of the nine partial products are accumulated in fp32 (gemm1x1s.hip).  Same
                       inputs / outputs / epilogue; per-product error <= 2^-23 relative, i.e. below the rounding of the
                       fp32 accumulation -- NOT bit-identical to w_split = 0.  Only shapes the LDS-DMA GEMM covers
-                      (pointwise, or K x K with Cin % 32 == 0; 16-byte aligned x; no BN prologue), else DH_EUNSUPPORTED */
+                      (pointwise, or K x K with Cin % 32 == 0; 16-byte aligned x; no BN prologue), else DH_EUNSUPPORTED.
+                      3 ("bf16x2") / 4 ("bf16"): the reduced-precision members of the same family, `w` packed by
+                      dh_conv2d_pack_weights_parts_host with parts = 2 / 1.  Operands are split by repeated round-to-nearest-even
+                      (x1 = bf16(x), x2 = bf16(x - x1)), activations after the optional ReLU prologue; with P parts every output is
+                      sum_k sum_{i + j <= P + 1} a_i[k] b_j[k] -- three products (a2 b1, a1 b2, a1 b1; ~2^-16 per product) or one
+                      (a1 b1; ~2^-8) instead of six, each exact, fp32 accumulation, smallest first, K ascending in every tiling; the
+                      fp32 epilogue is unchanged.  Same shapes, same refusals as 1; any other value is DH_EINVAL */
   int32_t res2_down; /* 1: res2 is at HALF the output resolution, [N, OH/2, OW/2, Cout]: out(oh, ow) += res2(oh/2, ow/2), i.e.
                         add([., UpSampling2D((2, 2))(res2)]) with the up-sampling folded into the residual read
                         (reception.py:122-127: `b = UpSampling2D((2, 2))(b); x = add([a, b])` fused into the convolution
@@ -111,12 +117,18 @@ int dh_conv2d_pack_weights_host(const float* w_hwio_host, float* packed_host, in
  * [Kp/8][3 parts][Np][8]; same Kp / Np as dh_conv2d_packed_dims */
 int dh_conv2d_pack_weights_split_host(const float* w_hwio_host, uint16_t* packed_host, int KH, int KW, int Cin,
                                       int Cout);
+/* the same for `parts` = 3 / 2 / 1 bf16 parts per weight (w_split = 1 / 3 / 4): `packed_host` holds parts * Kp * Np uint16
+ * laid out [Kp/8][parts][Np][8]; parts = 3 is dh_conv2d_pack_weights_split_host byte for byte, the parts of a smaller
+ * mode are the leading parts of a larger one.  DH_EINVAL for any other `parts` */
+int dh_conv2d_pack_weights_parts_host(const float* w_hwio_host, uint16_t* packed_host, int KH, int KW, int Cin,
+                                      int Cout, int parts);
 /* tile_cfg < 0: library heuristic; 0..dh_conv2d_num_tile_cfgs()-1 forces a tiling (autotuning hook): 0..8 the general
  * implicit-GEMM kernel, 9..17 the same tile shapes on the LDS-DMA GEMM (pointwise, K x K with Cin % 32 == 0; also with a
  * BatchNormalization prologue when pointwise).  A tiling that does not cover the layer returns DH_EUNSUPPORTED.  All
  * tilings of a layer give the same bits. */
 int dh_conv2d_num_tile_cfgs(void);
-int dh_conv2d_num_split_tile_cfgs(void); /* tilings of the w_split = 1 kernels: tile_cfg in [0, this) */
+int dh_conv2d_num_split_tile_cfgs(void); /* tilings of the w_split = 1 / 3 / 4 kernels: tile_cfg in [0, this) for every mode;
+                                            a tiling a mode does not have answers DH_EUNSUPPORTED */
 int dh_conv2d_pick_tile_cfg(int M, int Cout);
 /* Inputs must be FINITE.  K is padded to the kernels' step with zero weights, and on the LDS-DMA GEMM a padded k slot of
  * a pixel holds the following floats in memory (the next pixel's first channels, clamped inside the buffer): an Inf / NaN
@@ -134,7 +146,7 @@ int dh_conv2d_uses_split_k(const dh_conv_args* a);
  * the 7x7 entry conv of spnet.py:317-322 on 256 x 256 frames.  Like the split-K rule it looks at the layer's geometry
  * only; such a layer ignores tile_cfg. */
 int dh_conv2d_uses_first_layer_kernel(const dh_conv_args* a);
-/* 1 when dh_conv2d_f32 would accept this convolution with w_split = 1 (every field but `w` / `w_split` filled in as for
+/* 1 when dh_conv2d_f32 would accept this convolution with w_split = 1, 3 or 4 -- one rule for the three modes (every field but `w` / `w_split` filled in as for
  * the launch): an LDS-DMA GEMM shape (pointwise, or K x K with Cin % 32 == 0, no fused up-sampling), 16-byte aligned
  * float input, no BN prologue, not a split-K layer, operands within the 32-bit buffer offsets of the kernel.  A
  * binding asks this BEFORE it packs the weights, so that a layer is never bound with a packing its launch rejects. */
