@@ -30,6 +30,17 @@ class DwArgs(C.Structure):
                [(n, i32) for n in ('N', 'H', 'W', 'C', 'ldx', 'ldy', 'KH', 'KW', 'PT', 'PL', 'pre_relu', 'up_in')]
 
 
+class DwsArgs(C.Structure):                      # == struct dh_dw_strided
+    _fields_ = [(n, vp) for n in ('x', 'w', 'y', 'pre_scale', 'pre_shift')] + \
+               [(n, i32) for n in ('N', 'H', 'W', 'C', 'ldx', 'ldy', 'OH', 'OW', 'KH', 'KW', 'SH', 'SW', 'PT', 'PL',
+                                   'pre_relu', 'reserved')]
+
+
+class ConvtArgs(C.Structure):                    # == struct dh_conv_transpose
+    _fields_ = [(n, vp) for n in ('x', 'w', 'y', 'pre_scale', 'pre_shift', 'res')] + \
+               [(n, i32) for n in ('N', 'H', 'W', 'Cin', 'ldx', 'Cout', 'ldy', 'ldr', 'Kp', 'Np', 'pre_relu', 'post_relu')]
+
+
 class PoolArgs(C.Structure):
     _fields_ = [(n, vp) for n in ('x', 'y')] + \
                [(n, i32) for n in ('N', 'H', 'W', 'C', 'ldx', 'OH', 'OW', 'ldy', 'KH', 'KW', 'SH', 'SW', 'PT',
@@ -68,6 +79,9 @@ SIGNATURES = {
     'dh_conv2d_f32': (C.c_int, [C.POINTER(ConvArgs), C.c_int, vp]),
     'dh_normalize_u8_f32': (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp]),
     'dh_dwconv2d_f32': (C.c_int, [C.POINTER(DwArgs), vp]),
+    'dh_dwconv2d_strided_f32': (C.c_int, [C.POINTER(DwsArgs), vp]),
+    'dh_conv2d_transpose2x2_num_tile_cfgs': (C.c_int, []),
+    'dh_conv2d_transpose2x2_f32': (C.c_int, [C.POINTER(ConvtArgs), C.c_int, vp]),
     'dh_conv2d_dw_group_f32': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(DwArgs), vp]),
     'dh_conv2d_pair_f32': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), vp]),
     'dh_conv2d_seg_f32': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvSeg), vp]),

@@ -14,6 +14,7 @@ static_assert(sizeof(dh_conv_seg) == 24, "dh_conv_seg layout");
 static_assert(sizeof(dh_conv_args) == 200 && offsetof(dh_conv_args, y_pool) == 192 && offsetof(dh_conv_args, x_resample) == 188,
               "dh_conv_args layout");
 static_assert(sizeof(dh_dw_args) == 88 && offsetof(dh_dw_args, up_in) == 84, "dh_dw_args layout");
+static_assert(sizeof(dh_dw_strided) == 104 && sizeof(dh_conv_transpose) == 96, "dh_dw_strided / dh_conv_transpose layout");
 static_assert(sizeof(dh_sam_args) == 112 && offsetof(dh_sam_args, xy_times_conf) == 108, "dh_sam_args layout");
 static inline int rc_of(hipError_t e) { return e == hipSuccess ? DH_OK : DH_ELAUNCH; }
 
@@ -162,6 +163,34 @@ int dh_dwconv2d_f32(const dh_dw_args* a, void* stream) {
   if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
   if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
   return launch_dwconv(*a, S(stream));
+}
+
+int dh_dwconv2d_strided_f32(const dh_dw_strided* a, void* stream) {
+  if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
+  if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
+  if (a->SH <= 0 || a->SW <= 0 || a->KH <= 0 || a->KW <= 0) return DH_EINVAL;
+  return launch_dwconv_strided(*a, S(stream));
+}
+
+int dh_conv2d_transpose2x2_num_tile_cfgs(void) { return convt2x2_num_cfgs(); }
+
+int dh_conv2d_transpose2x2_f32(const dh_conv_transpose* a, int tile_cfg, void* stream) {
+  if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
+  if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
+  if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->Cout > 0x7fffffff / 4) return DH_EINVAL;
+  if (tile_cfg >= convt2x2_num_cfgs()) return DH_EINVAL;
+  // the GEMM the kernel runs: rows = input pixels, 4 * Cout columns, output pixels addressed by the epilogue
+  dh_conv_args g;
+  memset(&g, 0, sizeof(g));
+  g.x = a->x; g.w = a->w; g.y = a->y;
+  g.pre_scale = a->pre_scale; g.pre_shift = a->pre_shift;
+  g.res1 = a->res; g.ldr1 = a->ldr;
+  g.N = a->N; g.H = g.OH = a->H; g.W = g.OW = a->W; g.Cin = g.K = a->Cin; g.ldx = a->ldx;
+  g.Cout = 4 * a->Cout; g.ldy = a->ldy;
+  g.KH = g.KW = g.SH = g.SW = 1;
+  g.Kp = a->Kp; g.Np = a->Np;
+  g.pre_relu = a->pre_relu; g.post_relu = a->post_relu;
+  return launch_convt2x2(g, a->Cout, tile_cfg, S(stream));
 }
 
 int dh_pool2d_f32(const dh_pool_args* a, void* stream) {

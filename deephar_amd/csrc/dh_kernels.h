@@ -10,6 +10,7 @@ namespace dh {
 using ConvArgs = dh_conv_args;
 using ConvSeg = dh_conv_seg;
 using DwArgs = dh_dw_args;
+using DwsArgs = dh_dw_strided;
 using PoolArgs = dh_pool_args;
 using EltArgs = dh_elt_args;
 using SamArgs = dh_sam_args;
@@ -34,6 +35,9 @@ int conv_split_parts(int w_split);   // bf16 parts per operand of a split packin
 bool conv_halo_eligible(const ConvArgs& a);
 int conv_halo_num_cfgs();
 int launch_dwconv(const DwArgs& a, hipStream_t s);
+int launch_dwconv_strided(const DwsArgs& a, hipStream_t s);
+int launch_convt2x2(const ConvArgs& gemm, int cb, int cfg, hipStream_t s);
+int convt2x2_num_cfgs();
 int launch_conv_dw_group(const ConvArgs& a, const DwArgs& d, hipStream_t s);
 int launch_conv_skinny_pair(const ConvArgs& a, const ConvArgs& b, hipStream_t s);
 int launch_conv_splitk_seg(const ConvArgs& a, const ConvSeg& seg, hipStream_t s);

@@ -113,6 +113,101 @@ __global__ __launch_bounds__(256) void dwconv_generic_kernel(const DwArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Strided depthwise conv (stride 2: the depthwise half of SeparableConv2D(strides=(2, 2)), SPNet's down-scaling unit with
+// downsampling_type='conv', common.py:70-86).  The tap loop of dwconv_kernel above at a stride: thread = (channel quad,
+// output row, strip of TW output columns); one kernel row at a time, its (TW - 1) * S + KS input pixels loaded once, the
+// BN / ReLU prologue applied on the way in and the zero padding AFTER it; every output sums kh ascending, kw ascending with
+// one fused multiply-add per tap -- the order of the stride-1 kernels, so an output is bit for bit the stride-1 output at
+// the same window position.
+// ------------------------------------------------------------------------------------------------
+template <int KS, int S, int TW>
+__global__ __launch_bounds__(256) void dwconv_strided_kernel(const DwsArgs p) {
+  const int c4n = p.C >> 2;
+  const int strips = (p.OW + TW - 1) / TW;
+  const long long total = (long long)p.N * p.OH * strips * c4n;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  constexpr int NIN = (TW - 1) * S + KS;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(idx % c4n) * 4;
+    long long t = idx / c4n;
+    const int st = (int)(t % strips); t /= strips;
+    const int oh = (int)(t % p.OH);
+    const int n = (int)(t / p.OH);
+    const int ow0 = st * TW;
+
+    const bool aff = p.pre_scale != nullptr;
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = zero;
+    if (aff) { sc = ld4(p.pre_scale + c); sh = ld4(p.pre_shift + c); }
+
+    float4 acc[TW];
+#pragma unroll
+    for (int i = 0; i < TW; ++i) acc[i] = zero;
+
+#pragma unroll 1
+    for (int kh = 0; kh < KS; ++kh) {
+      const int ih = oh * S - p.PT + kh;
+      const bool rok = (unsigned)ih < (unsigned)p.H;
+      const float* row = p.x + ((size_t)(n * p.H + (rok ? ih : 0)) * p.W) * p.ldx + c;
+      float4 in[NIN];                    // issued unconditionally (clamped), masked afterwards: no wait between them
+#pragma unroll
+      for (int j = 0; j < NIN; ++j) {
+        const int iw = ow0 * S - p.PL + j;
+        in[j] = ld4(row + (size_t)((unsigned)iw < (unsigned)p.W ? iw : 0) * p.ldx);
+      }
+      float4 wv[KS];
+#pragma unroll
+      for (int kw = 0; kw < KS; ++kw) wv[kw] = ld4(p.w + (size_t)(kh * KS + kw) * p.C + c);
+#pragma unroll
+      for (int j = 0; j < NIN; ++j) {
+        const int iw = ow0 * S - p.PL + j;
+        float4 v = in[j];
+        if (aff) v = fma4(v, sc, sh);
+        if (p.pre_relu) v = max4(v, zero);
+        if (!(rok && (unsigned)iw < (unsigned)p.W)) v = zero;
+        in[j] = v;
+      }
+#pragma unroll
+      for (int o = 0; o < TW; ++o)
+#pragma unroll
+        for (int kw = 0; kw < KS; ++kw) acc[o] = fma4(in[o * S + kw], wv[kw], acc[o]);
+    }
+    float* out = p.y + ((size_t)(n * p.OH + oh) * p.OW + ow0) * p.ldy + c;
+#pragma unroll
+    for (int i = 0; i < TW; ++i)
+      if (ow0 + i < p.OW) st4(out + (size_t)i * p.ldy, acc[i]);
+  }
+}
+
+// any channel count / alignment: one thread per output element, the same sums in the same order
+__global__ __launch_bounds__(256) void dwconv_strided_generic_kernel(const DwsArgs p) {
+  const long long total = (long long)p.N * p.OH * p.OW * p.C;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(idx % p.C);
+    long long t = idx / p.C;
+    const int ow = (int)(t % p.OW); t /= p.OW;
+    const int oh = (int)(t % p.OH);
+    const int n = (int)(t / p.OH);
+    float acc = 0.f;
+    for (int kh = 0; kh < p.KH; ++kh) {
+      const int ih = oh * p.SH - p.PT + kh;
+      for (int kw = 0; kw < p.KW; ++kw) {
+        const int iw = ow * p.SW - p.PL + kw;
+        float v = 0.f;
+        if ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) {
+          v = p.x[((size_t)(n * p.H + ih) * p.W + iw) * p.ldx + c];
+          if (p.pre_scale != nullptr) v = fmaf(v, p.pre_scale[c], p.pre_shift[c]);
+          if (p.pre_relu) v = fmaxf(v, 0.f);
+        }
+        acc = fmaf(v, p.w[(size_t)(kh * p.KW + kw) * p.C + c], acc);
+      }
+    }
+    p.y[((size_t)(n * p.OH + oh) * p.OW + ow) * p.ldy + c] = acc;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(256) void pool_kernel(const PoolArgs p) {
   constexpr int V = VEC ? 4 : 1;
@@ -321,6 +416,28 @@ int launch_dwconv(const DwArgs& a, hipStream_t s) {
   } else {
     const long long total = (long long)a.N * a.H * a.W * a.C;
     hipLaunchKernelGGL(dwconv_generic_kernel, dim3(grid_for(total)), dim3(256), 0, s, a);
+  }
+  return check_launch();
+}
+
+int launch_dwconv_strided(const DwsArgs& a, hipStream_t s) {
+  if (a.N <= 0 || a.C <= 0 || a.H <= 0 || a.W <= 0 || a.OH <= 0 || a.OW <= 0 || a.PT < 0 || a.PL < 0 || a.ldx < a.C ||
+      a.ldy < a.C)
+    return DH_EINVAL;
+  if (!(a.KH == a.KW && (a.KW == 3 || a.KW == 5) && a.SH == 2 && a.SW == 2)) return DH_EUNSUPPORTED;
+  // every window starts inside the padded frame: the last one may hang over the bottom / right edge (zero padding)
+  if ((a.OH - 1) * a.SH - a.PT >= a.H || (a.OW - 1) * a.SW - a.PL >= a.W) return DH_EINVAL;
+  const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && al16(a.x) && al16(a.y) &&
+                   al16(a.w) && (a.pre_scale == nullptr || (al16(a.pre_scale) && al16(a.pre_shift)));
+  if (vec) {
+    constexpr int TW = 4;
+    const long long total = (long long)a.N * a.OH * ((a.OW + TW - 1) / TW) * (a.C / 4);
+    const dim3 g(grid_for(total)), b(256);
+    if (a.KW == 5) hipLaunchKernelGGL((dwconv_strided_kernel<5, 2, TW>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((dwconv_strided_kernel<3, 2, TW>), g, b, 0, s, a);
+  } else {
+    const long long total = (long long)a.N * a.OH * a.OW * a.C;
+    hipLaunchKernelGGL(dwconv_strided_generic_kernel, dim3(grid_for(total)), dim3(256), 0, s, a);
   }
   return check_launch();
 }

@@ -63,6 +63,23 @@ class WeightStore:
             self.conv[key] = ent
         return ent[0], ent[1], ent[2]
 
+    CONVT = 'convt'       # packing key of a Conv2DTranspose kernel in `conv` (beside the dh_conv_args.w_split codes)
+
+    def convt_weight(self, p):
+        """Keras Conv2DTranspose kernel [2, 2, Cout, Cin] as the packed [Cin, 4 * Cout] B operand of the depth-to-space
+        GEMM (packing.pack_convt); kept in `conv` like every packed GEMM weight."""
+        key = (id(p), self.CONVT)
+        ent = self.conv.get(key)
+        if ent is None or ent[3] != p.version:
+            packed, kp, np_ = packing.pack_convt(self._require(p))
+            if ent is None:
+                ent = (self._dev(packed), kp, np_, p.version)
+            else:
+                ent[0].copy_(self._dev(packed))
+                ent = (ent[0], kp, np_, p.version)
+            self.conv[key] = ent
+        return ent[0], ent[1], ent[2]
+
     def dw_weight(self, p):
         ent = self.dw.get(id(p))
         if ent is None or ent[1] != p.version:
@@ -298,6 +315,35 @@ class BoundPlan:
                 self.calls.append((lib.dh_conv2d_seg_f32, (C.byref(args), C.byref(seg)), s))
                 return
             self.calls.append((lib.dh_conv2d_f32, (C.byref(args), a.get('tile_cfg', -1)), s))
+        elif k == 'dwconv' and (a.get('sh', 1), a.get('sw', 1)) != (1, 1):
+            x, y = s.ins['x'], s.outs['y']             # the depthwise half of a strided SeparableConv2D
+            args = _lib.DwsArgs()
+            args.x, args.w, args.y = P(x), self.store.dw_weight(s.params['w']).data_ptr(), P(y)
+            if 'pre_bn' in s.params:
+                sc, sh = self.store.bn_affine(s.params['pre_bn'])
+                args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
+            args.N, args.H, args.W, args.C = n * x.lead(3), x.shape[-3], x.shape[-2], x.C
+            args.OH, args.OW, args.ldx, args.ldy = y.shape[-3], y.shape[-2], x.ld, y.ld
+            args.KH, args.KW, args.SH, args.SW, args.PT, args.PL = a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']
+            args.pre_relu = a['pre_relu']
+            self._keep.append(args)
+            self.calls.append((lib.dh_dwconv2d_strided_f32, (C.byref(args),), s))
+        elif k == 'convtranspose':
+            x, y = s.ins['x'], s.outs['y']             # Conv2DTranspose((2, 2), strides=(2, 2)): always the fp32 path,
+            args = _lib.ConvtArgs()                    # whatever plan.gemm_precision says
+            wt, kp, np_ = self.store.convt_weight(s.params['w'])
+            args.x, args.w, args.y = P(x), wt.data_ptr(), P(y)
+            if 'pre_bn' in s.params:
+                sc, sh = self.store.bn_affine(s.params['pre_bn'])
+                args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
+            r1 = s.ins.get('res1')
+            if r1 is not None:
+                args.res, args.ldr = P(r1), r1.ld
+            args.N, args.H, args.W, args.Cin, args.ldx = n * x.lead(3), x.shape[-3], x.shape[-2], x.C, x.ld
+            args.Cout, args.ldy, args.Kp, args.Np = a['Cout'], y.ld, kp, np_
+            args.pre_relu, args.post_relu = a['pre_relu'], a['post_relu']
+            self._keep.append(args)
+            self.calls.append((lib.dh_conv2d_transpose2x2_f32, (C.byref(args), a.get('tile_cfg', -1)), s))
         elif k == 'dwconv':
             x, y = s.ins['x'], s.outs['y']
             args = _lib.DwArgs()
@@ -531,6 +577,8 @@ class BoundPlan:
                 continue
             fd, ad, sd = self.calls[j]
             if sc.kind != 'conv' or sd.kind != 'dwconv' or sd.wait or i in self.noop_calls or fc is lib.dh_conv2d_dw_group_f32:
+                continue
+            if fd is not lib.dh_dwconv2d_f32:          # (a strided depthwise step has its own entry point and no grouped form)
                 continue
             # which pairs: the two halves of one unit, both reading its input.  Whether they may run as one grid is the pair
             # path's test: neither reads or overwrites what the other writes (the memory plan re-uses space: the depthwise
@@ -921,7 +969,9 @@ class Executor:
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             for s in self.plan.steps:
                 for role, p in s.params.items():
-                    if role == 'w' and s.kind != 'dwconv':
+                    if role == 'w' and s.kind == 'convtranspose':
+                        self.store.convt_weight(p)
+                    elif role == 'w' and s.kind != 'dwconv':
                         for (pid, split) in [k_ for k_ in self.store.conv if k_[0] == id(p)]:
                             self.store.conv_weight(p, split=split)
                     elif role == 'w':

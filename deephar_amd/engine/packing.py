@@ -19,6 +19,22 @@ def pack_conv(w_hwio):
     return out, kp.value, np_.value
 
 
+def convt_matrix(w):
+    """Keras Conv2DTranspose kernel [2, 2, Cout, Cin] -> the [1, 1, Cin, 4 * Cout] pointwise kernel of the GEMM
+    dh_conv2d_transpose2x2_f32 runs: column (2 a + b) * Cout + co holds W[a, b, co, :]."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    kh, kw, cout, cin = w.shape
+    if (kh, kw) != (2, 2):
+        raise ValueError('only 2x2 transposed-convolution kernels are packed, got %dx%d' % (kh, kw))
+    return np.ascontiguousarray(w.transpose(3, 0, 1, 2)).reshape(1, 1, cin, 4 * cout)
+
+
+def pack_convt(w):
+    """Keras Conv2DTranspose kernel [2, 2, Cout, Cin] -> ([Kp/4][Np][4] float32, Kp, Np): the [Cin, 4 * Cout] B operand
+    through the pointwise packer; the four column blocks are contiguous, the padding to Np follows the last one."""
+    return pack_conv(convt_matrix(w))
+
+
 HALO_CHUNK = 16      # channels per resident chunk of csrc/conv_halo.hip
 
 

@@ -38,6 +38,9 @@ Fusion rules (what the reference leaves to TensorFlow as separate kernels):
   R14 segments: [r06] a pooling that fills the first channels of a concatenation whose only reader is a convolution on the
                 skinny-conv kernel (the head's second residual unit, spnet.py:139-141) is not written out: that kernel reads
                 concatenate([pool(x), x2]) in place (dh_conv2d_seg_f32).  Bit-identical.
+  R15 learned : [downsampling_type='conv', common.py:70-108] a strided SeparableConv2D is a strided depthwise step plus the
+                pointwise convolution at the reduced resolution; BN -> ReLU -> Conv2DTranspose((2, 2), strides=(2, 2)) -> add is
+                ONE transposed-convolution step (prologue, depth-to-space GEMM, residual at the output resolution).
   (R10 / R10b / R10c: sibling convolutions of one tensor merged into one launch -- see the passes below.)
 Every rule that can be switched off has a field in engine/rules.py (RuleSet); a plan is built under ONE RuleSet (build_plan)
 and records it as Plan.rules.
@@ -163,6 +166,8 @@ class Step:
             y = self.outs['y']
             m = y.npix // (4 if a.get('up2') else 1)
             return 2.0 * n * m * a['K'] * a['Cout']
+        if self.kind == 'convtranspose':
+            return 2.0 * n * self.outs['y'].npix * a['K'] * a['Cout']
         if self.kind == 'dwconv':
             y = self.outs['y']
             return 2.0 * n * y.npix * y.C * a['kh'] * a['kw']
@@ -1059,7 +1064,10 @@ class Planner:
         # (profiles/r02_sepconv_fusion_study.md; the kernel lives in the history at commit 5d88aa8); a one-launch kernel
         # for the 8 x 8 level (frame, depthwise result and A operand all resident in LDS) was built in round 4,
         # bit-identical and neutral: 23-25 us against 11.5 + 15.5 us, step time unchanged (profiles/r04_sepconv8_study.md)
-        mid = self.new_value(node.inputs[0].shape)
+        strided = (a.get('sh', 1), a.get('sw', 1)) != (1, 1)
+        # a strided separable convolution (SPNet's down-scaling unit with downsampling_type='conv', common.py:70-86): the
+        # depthwise half runs at the stride (dh_dwconv2d_strided_f32), the pointwise half at the reduced resolution
+        mid = self.new_value(tuple(node.outputs[0].shape[:-1]) + (node.inputs[0].shape[-1],) if strided else node.inputs[0].shape)
         params = dict(w=layer.params[0])
         if pre_bn is not None:
             params['pre_bn'] = pre_bn
@@ -1071,10 +1079,49 @@ class Planner:
                 x, up_in = x.low, 1
             else:
                 x = self._realize_up(x)
-        self.emit('dwconv', dict(x=x), dict(y=mid),
-                  dict(kh=a['kh'], kw=a['kw'], pt=a['pt'], pl=a['pl'], pre_relu=int(pre_relu), up_in=up_in), params,
-                  node.name + '/dw')
+        dw = dict(kh=a['kh'], kw=a['kw'], pt=a['pt'], pl=a['pl'], pre_relu=int(pre_relu), up_in=up_in)
+        if strided:
+            dw.update(sh=a['sh'], sw=a['sw'])
+        self.emit('dwconv', dict(x=x), dict(y=mid), dw, params, node.name + '/dw')
         self._emit_conv(mid, None, False, layer.params[1], pw, node.outputs[0], node.name + '/pw')
+
+    def op_convtranspose(self, node):
+        """Conv2DTranspose((2, 2), strides=(2, 2)) -- SPNet's up-scaling unit with downsampling_type='conv' (common.py:
+        103-106): ONE step, a GEMM over the input pixels whose four column blocks go to the four output pixels
+        (dh_conv2d_transpose2x2_f32).  The BatchNormalization + ReLU in front of it are its prologue (R1); the lateral
+        add([xp, lp[i]]) right behind the unit (spnet.py:303) is its residual, read at the OUTPUT resolution -- when the add
+        has two operands, the other one exists and nobody else reads the unit's result (what R2 asks of a convolution's first
+        residual); a ReLU behind that folds in too.  Switch: RuleSet.split_adds (off: the add is an element-wise launch)."""
+        x, pre_bn, pre_relu = self._prologue(node.inputs[0])
+        if isinstance(x, _UpView):
+            x = self._realize_up(x)
+        if isinstance(x, _PoolView):
+            x = self._realize_pool(x)
+        t, res, post_relu = node.outputs[0], None, False
+        if self.rules.split_adds:
+            n = self.sole_consumer(t, 'add')
+            if n is not None and len(n.inputs) == 2:
+                other = [q for q in n.inputs if q.uid != t.uid]
+                if len(other) == 1 and self.available(other[0]):
+                    res = self.materialize(other[0])
+                    self.absorbed.add(n.uid)
+                    t = n.outputs[0]
+                    n = self.sole_consumer(t, 'relu')
+                    if n is not None:
+                        post_relu = True
+                        self.absorbed.add(n.uid)
+                        t = n.outputs[0]
+        y = self.out_value_for(t)
+        attrs = dict(kh=2, kw=2, sh=2, sw=2, Cin=x.C, Cout=node.attrs['filters'], K=x.C, pre_relu=int(pre_relu),
+                     post_relu=int(post_relu))
+        ins = dict(x=x)
+        if res is not None:
+            ins['res1'] = res
+        params = dict(w=node.layers['convt'].params[0])
+        if pre_bn is not None:
+            params['pre_bn'] = pre_bn
+        self.emit('convtranspose', ins, dict(y=y), attrs, params, node.name)
+        self.val[t.uid] = y
 
     # ---- glue ------------------------------------------------------------------------------------------
     def op_add(self, node):

@@ -1,7 +1,9 @@
 """Serialise a bound plan for the C-level executor of the library (include/deephar_hip.h: dh_plan_create / dh_forward /
 dh_plan_destroy -- SURVEY.md 8b's plan / execute pair): a host written in C or C++ runs the model without Python.
 
-Blob (little endian), version 2 (version 1 = float inputs only, no `u8 bytes` / `dtype`, still read by the library):
+Blob (little endian), version 2 (version 1 = float inputs only, no `u8 bytes` / `dtype`, still read by the library);
+a plan with a strided depthwise or a transposed-convolution step (downsampling_type='conv') is written as version 3: the
+same layout with the two further function ids -- every other plan stays version 2, byte for byte what it was:
     header   'DHPL' u32 version | i32 batch n | u64 arena bytes | u64 weight bytes | u32 #inputs | u32 #outputs | u32 #steps
              | u64 u8 bytes (size of region 3: the byte staging buffers of a uint8-input plan, 0 otherwise)
     inputs   per input : u64 tagged pointer of the buffer dh_forward copies the caller's data into (region 1: the plan's
@@ -29,7 +31,8 @@ FUNCTIONS = ['dh_conv2d_f32', 'dh_dwconv2d_f32', 'dh_pool2d_f32', 'dh_upsample2x
              'dh_softargmax2d_f32', 'dh_context_aggregation_f32', 'dh_depth_means_f32', 'dh_softargmax1d_f32',
              'dh_kronecker_f32', 'dh_global_maxmin_softmax_f32', 'dh_copy_channels_f32', 'dh_zeropad2d_f32',
              'dh_depth_from_maps_f32', 'dh_softargmax2d_context_f32', 'dh_normalize_u8_f32', 'dh_conv2d_dw_group_f32',
-             'dh_conv2d_pair_f32', 'dh_conv2d_seg_f32']
+             'dh_conv2d_pair_f32', 'dh_conv2d_seg_f32', 'dh_dwconv2d_strided_f32', 'dh_conv2d_transpose2x2_f32']
+V3_FUNCTIONS = FUNCTIONS.index('dh_dwconv2d_strided_f32')     # function ids from here on make a blob version 3
 ARENA, WEIGHTS, BYTES = 1, 2, 3
 
 
@@ -130,7 +133,8 @@ def dump_plan(model, batch, u8_norm=None):
             payload = _scalars(sig, args, reg)
         steps.append(struct.pack('<II', names[name], len(payload)) + payload)
     plan = bp.plan
-    head = MAGIC + struct.pack('<IiQQIIIQ', VERSION, bp.n, bp.arena.numel() * 4, (reg.size + 255) & ~255,
+    version = 3 if any(struct.unpack_from('<I', st)[0] >= V3_FUNCTIONS for st in steps) else VERSION
+    head = MAGIC + struct.pack('<IiQQIIIQ', version, bp.n, bp.arena.numel() * 4, (reg.size + 255) & ~255,
                                len(plan.inputs), len(plan.outputs), len(steps), reg.u8_size)
     ins = b''
     for v in plan.inputs:

@@ -161,6 +161,63 @@ def dwconv2d(x, dw_kernel, pre_scale=None, pre_shift=None, pre_relu=False, up_in
     return y
 
 
+def dwconv2d_strided(x, dw_kernel, strides=(2, 2), pre_scale=None, pre_shift=None, pre_relu=False, channels=None, out=None):
+    """Depthwise conv at a stride, TF-SAME (dh_dwconv2d_strided_f32: the depthwise half of SeparableConv2D(strides=(2, 2))).
+    dw_kernel numpy [kh,kw,C,1].  channels: x is [N,H,W,ldx] with ldx >= C and only its first C channels are read;
+    out: a preallocated [N,OH,OW,ldy] tensor (ldy >= C) whose first C channels are written."""
+    torch = _t()
+    _chk(x, pre_scale, pre_shift, out)
+    lib = _lib.load()
+    kh, kw, c, _ = dw_kernel.shape
+    n, h, w_, ldx = x.shape
+    assert (channels or ldx) == c
+    pt, _, oh = same_pad(h, kh, strides[0])
+    pl, _, ow = same_pad(w_, kw, strides[1])
+    wt = torch.from_numpy(np.ascontiguousarray(dw_kernel.reshape(kh * kw, c), np.float32)).to(x.device)
+    y = out if out is not None else torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device)
+    assert tuple(y.shape[:3]) == (n, oh, ow) and y.shape[3] >= c
+    a = _lib.DwsArgs()
+    a.x, a.w, a.y, a.pre_scale, a.pre_shift = _p(x), _p(wt), _p(y), _p(pre_scale), _p(pre_shift)
+    a.N, a.H, a.W, a.C, a.ldx, a.ldy = n, h, w_, c, ldx, y.shape[3]
+    a.OH, a.OW = oh, ow
+    a.KH, a.KW, a.SH, a.SW, a.PT, a.PL, a.pre_relu = kh, kw, strides[0], strides[1], pt, pl, int(pre_relu)
+    _lib.check(lib.dh_dwconv2d_strided_f32(C.byref(a), _stream()), 'dh_dwconv2d_strided_f32')
+    return y
+
+
+def pack_convt_weight(w, device='cuda'):
+    """Keras Conv2DTranspose kernel [2,2,Cout,Cin] (numpy) -> (packed device tensor, Kp, Np) for conv2d_transpose."""
+    torch = _t()
+    packed, kp, np_ = packing.pack_convt(np.asarray(w, np.float32))
+    return torch.from_numpy(packed).to(device), kp, np_
+
+
+def conv2d_transpose(x, w, strides=(2, 2), pre_scale=None, pre_shift=None, pre_relu=False, res=None, post_relu=False,
+                     tile_cfg=-1, packed=None, channels=None, out=None):
+    """Conv2DTranspose((2, 2), strides=(2, 2), use_bias=False) with the fused BN / ReLU prologue and residual / ReLU
+    epilogue of dh_conv2d_transpose2x2_f32.  x [N,H,W,Cin]; w numpy, Keras layout [2,2,Cout,Cin]; res [N,2H,2W,ldr] at the
+    OUTPUT resolution.  channels: x is [N,H,W,ldx] and only its first Cin channels are read; out: a preallocated
+    [N,2H,2W,ldy] tensor whose first Cout channels are written.  Always fp32 (no gemm_precision applies)."""
+    torch = _t()
+    kh, kw, cout, cin = w.shape
+    if (kh, kw) != (2, 2) or tuple(strides) != (2, 2):
+        raise NotImplementedError('conv2d_transpose is built for kernel_size=(2, 2), strides=(2, 2) only')
+    _chk(x, pre_scale, pre_shift, res, out)
+    lib = _lib.load()
+    n, h, w_, ldx = x.shape
+    assert (channels or ldx) == cin
+    wt, kp, np_ = packed if packed is not None else pack_convt_weight(w, x.device)
+    y = out if out is not None else torch.empty((n, 2 * h, 2 * w_, cout), dtype=torch.float32, device=x.device)
+    assert tuple(y.shape[:3]) == (n, 2 * h, 2 * w_) and y.shape[3] >= cout
+    a = _lib.ConvtArgs()
+    a.x, a.w, a.y, a.pre_scale, a.pre_shift, a.res = _p(x), _p(wt), _p(y), _p(pre_scale), _p(pre_shift), _p(res)
+    a.N, a.H, a.W, a.Cin, a.ldx = n, h, w_, cin, ldx
+    a.Cout, a.ldy, a.ldr = cout, y.shape[3], res.shape[-1] if res is not None else 0
+    a.Kp, a.Np, a.pre_relu, a.post_relu = kp, np_, int(pre_relu), int(post_relu)
+    _lib.check(lib.dh_conv2d_transpose2x2_f32(C.byref(a), tile_cfg, _stream()), 'dh_conv2d_transpose2x2_f32')
+    return y
+
+
 def pool2d(x, pool=(2, 2), strides=None, padding='valid', mode=0):
     torch = _t()
     _chk(x)

@@ -26,7 +26,7 @@ class Param:
         self.key = key          # '<scope>/<layer>/<weight>'
         self.name = name        # weight name
         self.shape = tuple(int(s) for s in shape)
-        self.role = role        # 'conv' | 'depthwise' | 'beta' | 'mean' | 'var' | 'gamma' | 'frozen'
+        self.role = role        # 'conv' | 'convt' | 'depthwise' | 'beta' | 'mean' | 'var' | 'gamma' | 'frozen'
         self.value = None       # np.float32 array once set
         self.version = 0        # bumped on every set (device copies are refreshed lazily)
         self.fan_in = None
@@ -40,7 +40,7 @@ class Param:
 
 
 class Layer:
-    """A weight-owning layer record (Conv2D / SeparableConv2D / BatchNormalization)."""
+    """A weight-owning layer record (Conv2D / SeparableConv2D / Conv2DTranspose / BatchNormalization)."""
 
     def __init__(self, cls, name, scope, params):
         self.cls = cls
@@ -146,7 +146,8 @@ def make_layer(cls, name, specs):
     """specs: list of (weight_name, shape, role)."""
     scope = _state.scope
     lname = name or auto_name({'Conv2D': 'conv2d', 'SeparableConv2D': 'separable_conv2d',
-                               'BatchNormalization': 'batch_normalization'}[cls])
+                               'BatchNormalization': 'batch_normalization',
+                               'Conv2DTranspose': 'conv2d_transpose'}[cls])
     params = [Param('%s/%s/%s' % (scope, lname, w), w, shape, role) for (w, shape, role) in specs]
     return Layer(cls, lname, scope, params)
 

@@ -3,7 +3,7 @@
 Same function names, argument meaning and composition order as the reference helpers, so the model
 builders in deephar_amd/models read like deephar/models/*.py.  Nothing here computes: nodes are fused and
 lowered to gfx950 kernels by deephar_amd/engine.  Helpers the reference defines but no experiment calls
-(localconv1d, deconv, bn_act_conv, dense, ... -- SURVEY.md section 2) are intentionally absent.
+(localconv1d, bn_act_conv, dense, ... -- SURVEY.md section 2) are intentionally absent.
 """
 import numpy as np
 
@@ -71,8 +71,6 @@ conv = conv2d
 def sepconv2d(x, filters, kernel_size, strides=(1, 1), padding='same', name=None):
     """layers.sepconv2d (layers.py:74-80): SeparableConv2D(use_bias=False), depth_multiplier 1."""
     size, strides = _pair(kernel_size), _pair(strides)
-    if strides != (1, 1):
-        raise NotImplementedError('strided SeparableConv2D is not used by any experiment script')
     cin = x.shape[-1]
     oh, ow, pt, pl = _conv_out(x.shape, size, strides, padding)
     layer = G.make_layer('SeparableConv2D', name, [
@@ -80,8 +78,24 @@ def sepconv2d(x, filters, kernel_size, strides=(1, 1), padding='same', name=None
         ('pointwise_kernel', (1, 1, cin, filters), 'conv')])
     layer.params[0].fan_in = size[0] * size[1]
     layer.params[1].fan_in = cin
-    attrs = dict(kh=size[0], kw=size[1], pt=pt, pl=pl, filters=filters)
+    attrs = dict(kh=size[0], kw=size[1], sh=strides[0], sw=strides[1], pt=pt, pl=pl, filters=filters)
     return G.emit('sepconv', [x], [x.shape[:-3] + (oh, ow, filters)], attrs, dict(sepconv=layer),
+                  name=layer.name)[0]
+
+
+def conv2dtranspose(x, filters, kernel_size, strides=(1, 1), padding='same', name=None):
+    """layers.conv2dtranspose (layers.py:83-89): Conv2DTranspose(use_bias=False).  The kernel is Keras' [kh, kw, Cout, Cin];
+    only kernel = strides = (2, 2) is built (what common.upscaling_unit asks for, common.py:103-106): every output pixel
+    (2i + a, 2j + b) sees exactly one tap, y = W[a, b] @ x[i, j], and the output is exactly [.., 2H, 2W, filters]."""
+    size, strides = _pair(kernel_size), _pair(strides)
+    if size != (2, 2) or strides != (2, 2) or padding != 'same':
+        raise NotImplementedError("Conv2DTranspose is built for kernel_size=(2, 2), strides=(2, 2), padding='same' only "
+                                  '(got kernel_size=%s, strides=%s, padding=%r)' % (size, strides, padding))
+    cin = x.shape[-1]
+    layer = G.make_layer('Conv2DTranspose', name, [('kernel', (2, 2, filters, cin), 'convt')])
+    layer.params[0].fan_in = cin              # one tap per output pixel
+    shape = x.shape[:-3] + (2 * x.shape[-3], 2 * x.shape[-2], filters)
+    return G.emit('convtranspose', [x], [shape], dict(kh=2, kw=2, sh=2, sw=2, filters=filters), dict(convt=layer),
                   name=layer.name)[0]
 
 

@@ -43,7 +43,7 @@ def residual_unit(x, kernel_size, strides=(1, 1), out_size=None, convtype='depth
 
 
 def downscaling_unit(x, cfg, out_size=None, name=None):
-    """common.py:70-86 (max-pooling flavour; strided-conv flavour keeps the reference's s1=(2,2))."""
+    """common.py:70-86: 'maxpooling' pools 2x2 in front of a stride-1 residual unit, 'conv' is a stride-2 residual unit."""
     out_size = x.shape[-1] if out_size is None else out_size
     s1 = (2, 2) if cfg.downsampling_type == 'conv' else (1, 1)
     if cfg.downsampling_type == 'maxpooling':
@@ -52,11 +52,14 @@ def downscaling_unit(x, cfg, out_size=None, name=None):
 
 
 def upscaling_unit(x, cfg, out_size=None, name=None):
-    """common.py:89-108; the transposed-conv flavour (downsampling_type='conv') is used by no experiment."""
+    """common.py:89-108.  'maxpooling': a residual unit on the nearest up-sampled tensor; 'conv' (learned resampling,
+    common.py:103-106): BN -> ReLU -> Conv2DTranspose((2, 2), strides=(2, 2))."""
     out_size = x.shape[-1] if out_size is None else out_size
-    if cfg.downsampling_type != 'maxpooling':
-        raise NotImplementedError("Conv2DTranspose up-scaling (downsampling_type='conv') is not on the hot path")
-    return residual_unit(L.upsampling2d(x, (2, 2)), cfg.kernel_size, out_size=out_size, name=appstr(name, '_r0'))
+    if cfg.downsampling_type == 'maxpooling':
+        return residual_unit(L.upsampling2d(x, (2, 2)), cfg.kernel_size, out_size=out_size, name=appstr(name, '_r0'))
+    x = L.BatchNormalization(x, name=appstr(name, '_bn1'))
+    x = L.relu(x, name=appstr(name, '_act1'))
+    return L.conv2dtranspose(x, out_size, (2, 2), strides=(2, 2), name=appstr(name, '_convtrans1'))
 
 
 # Aliases (common.py:158-160)

@@ -93,6 +93,10 @@ def init_synthetic(model, seed=0, logit_std=6.0):
             layer = n.layers['sepconv']
             v1 = set_conv(layer.params[0], layer.params[0].fan_in, 2.0, var + mu * mu)
             out = (0.0, set_conv(layer.params[1], layer.params[1].fan_in, 1.0, v1))
+        elif op == 'convtranspose':
+            # Conv2DTranspose((2, 2), strides=(2, 2)): every output pixel sees ONE tap, so the fan-in is Cin
+            p = n.layers['convt'].params[0]
+            out = (0.0, set_conv(p, p.fan_in, 2.0, var + mu * mu))
         elif op == 'bn':
             layer = n.layers['bn']
             for p in layer.params:

@@ -168,7 +168,7 @@ int dh_conv2d_f32(const dh_conv_args* a, int tile_cfg, void* stream);
 int dh_normalize_u8_f32(const uint8_t* x, const float* lut, float* y, int64_t n_pixels, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * Depthwise KxK conv, stride 1, explicit padding: the depthwise half of keras SeparableConv2D
+ * Depthwise KxK conv, stride 1 (stride 2: dh_dwconv2d_strided_f32 below), explicit padding: the depthwise half of keras SeparableConv2D
  * (layers.py:74-80, 288-301; depth_multiplier 1, no bias).  w is [KH,KW,C] (= Keras [KH,KW,C,1]).
  * ------------------------------------------------------------------------------------------------- */
 typedef struct dh_dw_args {
@@ -187,6 +187,64 @@ typedef struct dh_dw_args {
                     occupies what was tail padding of the struct: a caller that zero-initialises it is unchanged */
 } dh_dw_args;
 int dh_dwconv2d_f32(const dh_dw_args* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Strided depthwise KxK conv: the depthwise half of keras SeparableConv2D(k, strides=(2, 2), padding='same',
+ * use_bias=False) -- the stride-2 residual unit of SPNet's learned-resampling flavour (downsampling_type='conv':
+ * deephar/models/common.py:70-86, 25-67; layers.py:74-80), replaces the depthwise half of layers.sepconv2d at a stride.
+ *   y[n, oh, ow, c] = sum_{kh, kw} pro(x)[n, oh*SH - PT + kh, ow*SW - PL + kw, c] * w[kh, kw, c]
+ *   pro(v) = relu?( v * pre_scale[c] + pre_shift[c] ) on in-bounds taps, zero outside (padding AFTER the prologue).
+ * Padding is explicit (PT, PL): TF-"SAME" at stride 2 is asymmetric on even extents (k = 5: one row above, two below),
+ * the caller's arithmetic.  w is [KH, KW, C].  Built for KH = KW in {3, 5} and SH = SW = 2 (DH_EUNSUPPORTED otherwise);
+ * any ldx / ldy >= C (channel slabs of joint buffers), any C.  Taps are summed kh ascending, kw ascending, one fused
+ * multiply-add each -- the order of dh_dwconv2d_f32, so an output equals the stride-1 output at the same window position
+ * bit for bit.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_dw_strided {
+  const float* x;
+  const float* w;
+  float* y;
+  const float* pre_scale;
+  const float* pre_shift;
+  int32_t N, H, W, C, ldx, ldy;
+  int32_t OH, OW;
+  int32_t KH, KW, SH, SW, PT, PL;
+  int32_t pre_relu;
+  int32_t reserved; /* 0 */
+} dh_dw_strided;
+int dh_dwconv2d_strided_f32(const dh_dw_strided* a, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Conv2DTranspose(filters, (2, 2), strides=(2, 2), padding='same', use_bias=False) (+ folded BatchNormalization / ReLU
+ * in front, add / ReLU behind): replaces layers.conv2dtranspose (deephar/layers.py:83-89) as common.upscaling_unit uses
+ * it (deephar/models/common.py:103-106: BN -> ReLU -> Conv2DTranspose) and the pyramid's add([xp, lp[i]]) behind the
+ * unit (spnet.py:303).
+ *   y[n, 2i+a, 2j+b, co] = relu?( sum_ci W[a, b, co, ci] * pro(x)[n, i, j, ci] + res[n, 2i+a, 2j+b, co] )     (no kernel flip)
+ *   pro(v) = relu?( v * pre_scale[ci] + pre_shift[ci] );  x is [N, H, W, Cin], y and res are [N, 2H, 2W, Cout].
+ * One GEMM [N*H*W, Cin] x [Cin, 4*Cout] on the fp32 matrix cores with a depth-to-space store.  `w` is the Keras kernel
+ * [2, 2, Cout, Cin] re-ordered to the matrix B[ci][(2a + b) * Cout + co] and packed by dh_conv2d_pack_weights_host(B, .,
+ * 1, 1, Cin, 4 * Cout); Kp / Np are dh_conv2d_packed_dims(1, 1, Cin, 4 * Cout).  The four column blocks are contiguous
+ * (the padding to Np follows the last one); the kernel finds a column's block by comparison, for any Cout.
+ * K is summed ascending in every tiling: result bits depend on neither tile_cfg (< 0: library heuristic, else
+ * 0 .. dh_conv2d_transpose2x2_num_tile_cfgs() - 1) nor batch size.  This layer has no reduced-precision form: under every
+ * gemm_precision of the engine it stays fp32 (4 % of the FLOPs of a two-pyramid SPNet at 256 px, 11 % of an eight-pyramid one).
+ * Needs Cin % 4 == 0, ldx % 4 == 0, 16-byte aligned x (DH_EUNSUPPORTED otherwise); inputs must be finite (see dh_conv2d_f32).
+ * Other transposed-convolution geometries are not built.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_conv_transpose {
+  const float* x;
+  const float* w;
+  float* y;
+  const float* pre_scale;
+  const float* pre_shift;
+  const float* res; /* optional, at the OUTPUT resolution, pixel pitch ldr */
+  int32_t N, H, W, Cin, ldx;
+  int32_t Cout, ldy, ldr;
+  int32_t Kp, Np;
+  int32_t pre_relu, post_relu;
+} dh_conv_transpose;
+int dh_conv2d_transpose2x2_num_tile_cfgs(void);
+int dh_conv2d_transpose2x2_f32(const dh_conv_transpose* a, int tile_cfg, void* stream);
 
 /* [r06] The two independent first layers of a pre-activation residual unit in ONE launch (deephar/models/common.py:25-67:
  * `shortcut = conv2d(relu(BN(x)), out, (1, 1))` beside `sepconv2d(relu(BN(x)), ...)`, whose depthwise half is `dw`): the
