@@ -82,6 +82,9 @@ SIGNATURES = {
     'dh_dwconv2d_strided_f32': (C.c_int, [C.POINTER(DwsArgs), vp]),
     'dh_conv2d_transpose2x2_num_tile_cfgs': (C.c_int, []),
     'dh_conv2d_transpose2x2_f32': (C.c_int, [C.POINTER(ConvtArgs), C.c_int, vp]),
+    'dh_conv2d_transpose2x2_num_split_tile_cfgs': (C.c_int, []),
+    'dh_conv2d_transpose2x2_split_eligible': (C.c_int, [C.POINTER(ConvtArgs)]),
+    'dh_conv2d_transpose2x2_split_f32': (C.c_int, [C.POINTER(ConvtArgs), C.c_int, C.c_int, vp]),
     'dh_conv2d_dw_group_f32': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(DwArgs), vp]),
     'dh_conv2d_pair_f32': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), vp]),
     'dh_conv2d_seg_f32': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvSeg), vp]),

@@ -174,12 +174,8 @@ int dh_dwconv2d_strided_f32(const dh_dw_strided* a, void* stream) {
 
 int dh_conv2d_transpose2x2_num_tile_cfgs(void) { return convt2x2_num_cfgs(); }
 
-int dh_conv2d_transpose2x2_f32(const dh_conv_transpose* a, int tile_cfg, void* stream) {
-  if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
-  if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
-  if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->Cout > 0x7fffffff / 4) return DH_EINVAL;
-  if (tile_cfg >= convt2x2_num_cfgs()) return DH_EINVAL;
-  // the GEMM the kernel runs: rows = input pixels, 4 * Cout columns, output pixels addressed by the epilogue
+// the GEMM the transposed-convolution kernels run: rows = input pixels, 4 * Cout columns, output pixels addressed by the epilogue
+static dh_conv_args convt_gemm(const dh_conv_transpose* a) {
   dh_conv_args g;
   memset(&g, 0, sizeof(g));
   g.x = a->x; g.w = a->w; g.y = a->y;
@@ -190,7 +186,32 @@ int dh_conv2d_transpose2x2_f32(const dh_conv_transpose* a, int tile_cfg, void* s
   g.KH = g.KW = g.SH = g.SW = 1;
   g.Kp = a->Kp; g.Np = a->Np;
   g.pre_relu = a->pre_relu; g.post_relu = a->post_relu;
-  return launch_convt2x2(g, a->Cout, tile_cfg, S(stream));
+  return g;
+}
+
+int dh_conv2d_transpose2x2_f32(const dh_conv_transpose* a, int tile_cfg, void* stream) {
+  if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
+  if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
+  if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->Cout > 0x7fffffff / 4) return DH_EINVAL;
+  if (tile_cfg >= convt2x2_num_cfgs()) return DH_EINVAL;
+  return launch_convt2x2(convt_gemm(a), a->Cout, tile_cfg, S(stream));
+}
+
+int dh_conv2d_transpose2x2_num_split_tile_cfgs(void) { return convt2x2_split_num_cfgs(); }
+
+int dh_conv2d_transpose2x2_split_eligible(const dh_conv_transpose* a) {
+  if (a == nullptr || (a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return 0;
+  if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->Cout > 0x7fffffff / 4) return 0;
+  return convt2x2_split_eligible(convt_gemm(a), a->Cout) ? 1 : 0;
+}
+
+int dh_conv2d_transpose2x2_split_f32(const dh_conv_transpose* a, int parts, int tile_cfg, void* stream) {
+  if (parts < 1 || parts > 3) return DH_EINVAL;
+  if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
+  if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
+  if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->Cout > 0x7fffffff / 4) return DH_EINVAL;
+  if (tile_cfg >= convt2x2_split_num_cfgs()) return DH_EINVAL;
+  return launch_convt2x2_split(convt_gemm(a), a->Cout, parts, tile_cfg, S(stream));
 }
 
 int dh_pool2d_f32(const dh_pool_args* a, void* stream) {

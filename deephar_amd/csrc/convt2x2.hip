@@ -4,7 +4,7 @@
 // Kernel = strides, so every output pixel (2i + a, 2j + b) sees exactly ONE tap: y[n, 2i+a, 2j+b, :] = W[a, b] @ x[n, i, j, :].
 // That is one GEMM [M = N*H*W, K = Cin] x [Cin, 4 * Cout] whose column block (a, b) of row (n, i, j) is stored at pixel
 // (2i + a, 2j + b): the LDS-DMA main loop of gemm1x1.hip (fp32 MFMA, K ascending in every tiling -- the bits of an output
-// depend on neither tiling nor batch size) in front of a depth-to-space epilogue (gemm1x1.hip: d2s_epilogue).
+// depend on neither tiling nor batch size) in front of a depth-to-space epilogue (conv_common.h: d2s_epilogue).
 // Prologue: BatchNormalization (scale / shift) + ReLU on the input, as in the pointwise form.  Epilogue: an optional residual
 // read at the OUTPUT resolution (the pyramid's add([xp, lp[i]]) right behind the unit, spnet.py:303) and an optional ReLU.
 // This translation unit compiles gemm1x1.hip's kernel body a second time, for its own instantiations only.

@@ -38,6 +38,9 @@ int launch_dwconv(const DwArgs& a, hipStream_t s);
 int launch_dwconv_strided(const DwsArgs& a, hipStream_t s);
 int launch_convt2x2(const ConvArgs& gemm, int cb, int cfg, hipStream_t s);
 int convt2x2_num_cfgs();
+int launch_convt2x2_split(const ConvArgs& gemm, int cb, int parts, int cfg, hipStream_t s);
+bool convt2x2_split_eligible(const ConvArgs& gemm, int cb);
+int convt2x2_split_num_cfgs();
 int launch_conv_dw_group(const ConvArgs& a, const DwArgs& d, hipStream_t s);
 int launch_conv_skinny_pair(const ConvArgs& a, const ConvArgs& b, hipStream_t s);
 int launch_conv_splitk_seg(const ConvArgs& a, const ConvSeg& seg, hipStream_t s);

@@ -85,97 +85,6 @@ __device__ __forceinline__ void fetch_frags(const unsigned (&a_addr)[TM][4], uns
   if constexpr (TN > 2) fb[2] = lds_rd<BO + 1024>(b_addr);
 }
 
-// Depth-to-space epilogue of Conv2DTranspose((2, 2), strides=(2, 2)) -- the sibling of conv_epilogue's UP2 form: that one
-// replicates a column to four output pixels, this one routes four column BLOCKS to four output pixels.  The GEMM has
-// 4 * cb columns (p.Cout), column n = (2 a + b) * cb + co of row (frame, i, j) is channel co of output pixel
-// (2 i + a, 2 j + b); the optional residual p.res1 (pitch p.ldr1) is read at that OUTPUT pixel, then the optional ReLU.
-// Staged through the wave's LDS slab like conv_epilogue, so that stores are whole 16-byte channel quads (vec: cb, the
-// pitches and the pointers allow it; a quad never straddles two blocks then).
-template <int WM, int WN, int TM, int TN>
-__device__ __forceinline__ void d2s_epilogue(const ConvArgs& p, f32x16 (&acc)[TM][TN], float* smem, const int m0, const int n0,
-                                             const int M, const int vec, const int cb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int li = lane & 31, lh = lane >> 5;
-  constexpr int LDC = TN * 32 + 4, ROW4 = TN * 8, IT = 4 * TN;
-  float* sC = smem + wave * 32 * LDC;
-  const int hw = p.OH * p.OW;
-  const bool pow2 = (p.OW & (p.OW - 1)) == 0 && (hw & (hw - 1)) == 0;       // (uniform) shifts instead of integer divides
-  const int ow_sh = __ffs(p.OW) - 1, hw_sh = __ffs(hw) - 1;
-  // output pixel of GEMM row m, block q
-  auto out_pixel = [&](int m, int q) {
-    int fr, oh, ow;
-    if (pow2) {
-      fr = m >> hw_sh;
-      const int rem = m & (hw - 1);
-      oh = rem >> ow_sh;
-      ow = rem & (p.OW - 1);
-    } else {
-      fr = m / hw;
-      const int rem = m - fr * hw;
-      oh = rem / p.OW;
-      ow = rem - oh * p.OW;
-    }
-    return ((size_t)fr * 2 * p.OH + 2 * oh + (q >> 1)) * (2 * p.OW) + 2 * ow + (q & 1);
-  };
-  __syncthreads();                            // every wave is done with the operand stages
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    if (i > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // slab reads of the previous block
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sC[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDC + j * 32 + li] = acc[i][j][r];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // wave-private slab: no barrier needed
-    if (vec) {
-      constexpr int CH = IT < 4 ? IT : 4;     // rows per chunk: their residual quads are in flight before the first store
-#pragma unroll
-      for (int c0 = 0; c0 < IT; c0 += CH) {
-        float4 rr[CH];
-        size_t mo[CH];
-        int co[CH];
-        bool ok[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-          const int f = lane + 64 * (c0 + u);
-          const int row = f / ROW4, c4 = f - row * ROW4;
-          const int m = m0 + (wm * TM + i) * 32 + row;
-          const int n = n0 + wn * TN * 32 + c4 * 4;
-          ok[u] = m < M && n < p.Cout;
-          const int mc = ok[u] ? m : 0, nc = ok[u] ? n : 0;
-          const int q = (nc >= cb) + (nc >= 2 * cb) + (nc >= 3 * cb);
-          co[u] = nc - q * cb;
-          mo[u] = out_pixel(mc, q);
-          if (p.res1 != nullptr) rr[u] = ld4_stream(p.res1 + mo[u] * p.ldr1 + co[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-          const int f = lane + 64 * (c0 + u);
-          const int row = f / ROW4, c4 = f - row * ROW4;
-          float4 t = *reinterpret_cast<const float4*>(&sC[row * LDC + c4 * 4]);
-          if (p.res1 != nullptr) { t.x += rr[u].x; t.y += rr[u].y; t.z += rr[u].z; t.w += rr[u].w; }
-          if (p.post_relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
-          if (ok[u]) st4_stream(p.y + mo[u] * p.ldy + co[u], t);
-        }
-      }
-    } else {
-      for (int f = lane; f < 32 * TN * 32; f += 64) {
-        const int row = f / (TN * 32), c = f - row * (TN * 32);
-        const int m = m0 + (wm * TM + i) * 32 + row;
-        const int n = n0 + wn * TN * 32 + c;
-        if (m >= M || n >= p.Cout) continue;
-        const int q = (n >= cb) + (n >= 2 * cb) + (n >= 3 * cb);
-        const int ch = n - q * cb;
-        const size_t mo = out_pixel(m, q);
-        float t = sC[row * LDC + c];
-        if (p.res1 != nullptr) t += p.res1[mo * p.ldr1 + ch];
-        if (p.post_relu) t = fmaxf(t, 0.f);
-        p.y[mo * p.ldy + ch] = t;
-      }
-    }
-  }
-}
-
 // KXK: the same kernel as an implicit GEMM over a K x K (strided, zero-padded) convolution whose Cin is a multiple
 // of 32: K-step kt covers 32 channels of ONE filter tap, so each staged row is still one contiguous 128-byte run -- of
 // the tap's input pixel, or of a page of zeros when the tap falls into the padding (ReLU-on-load keeps zeros zero).
@@ -183,7 +92,7 @@ __device__ __forceinline__ void d2s_epilogue(const ConvArgs& p, f32x16 (&acc)[TM
 // kernel's blockIdx.x / gridDim.x, or its share of a grouped launch: conv_dw_group_kernel below), `smem` the work-group's
 // dynamic LDS; threads 0 .. WM * WN * 64 - 1 run it.
 // D2S: the main loop of the pointwise form in front of the depth-to-space epilogue of the transposed 2x2 / stride-2
-// convolution (convt2x2.hip: d2s_epilogue; `cb` = columns per output-pixel block).
+// convolution (conv_common.h: d2s_epilogue; `cb` = columns per output-pixel block).
 template <int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, bool PRE = false, bool D2S = false>
 __device__ __forceinline__ void gemm1x1_body(const ConvArgs& p, const int epi_vec, const int block, const int nblocks,
                                              float* const smem, const int cb = 0) {
@@ -417,8 +326,6 @@ __global__ __launch_bounds__(256) void conv_dw_group_kernel(const ConvArgs pc, c
                                                             reinterpret_cast<float4*>(smem));
   }
 }
-
-constexpr int kMaxPreKp = 4096;    // BN prologue: scale + shift tables of at most 2 x 16 KB in LDS
 
 #ifndef DH_CONVT_TU      // (convt2x2.hip includes this file for the kernel body above and brings its own launch side)
 

@@ -12,7 +12,7 @@ namespace {
 
 using dh::check_launch;
 
-enum Fn { F_CONV, F_DW, F_POOL, F_UPADD, F_ELT, F_SAM, F_CTX, F_DMEANS, F_SAM1D, F_KRON, F_GMM, F_COPY, F_ZPAD, F_DFM, F_SAMCTX, F_NORM, F_GROUP, F_PAIR, F_SEG, F_DWS, F_CONVT, F_COUNT };
+enum Fn { F_CONV, F_DW, F_POOL, F_UPADD, F_ELT, F_SAM, F_CTX, F_DMEANS, F_SAM1D, F_KRON, F_GMM, F_COPY, F_ZPAD, F_DFM, F_SAMCTX, F_NORM, F_GROUP, F_PAIR, F_SEG, F_DWS, F_CONVT, F_CONVTS, F_COUNT };
 
 struct Step { int fn; std::vector<unsigned char> payload; };
 struct In { uint64_t tag; size_t items; int u8; char* dst; };   // dst: where dh_forward copies the caller's data (patched)
@@ -71,6 +71,7 @@ int struct_pointers(int fn) {
     case F_SAMCTX: return 8;
     case F_DWS: return 5;
     case F_CONVT: return 6;
+    case F_CONVTS: return 6;
   }
   return -1;
 }
@@ -79,6 +80,7 @@ void struct_extra(int fn, int* nargs, unsigned* ptr_mask) {
   *nargs = 0;
   *ptr_mask = 0;
   if (fn == F_CONV || fn == F_CONVT) *nargs = 1;                 // tile_cfg
+  if (fn == F_CONVTS) *nargs = 2;                                // parts, tile_cfg
   if (fn == F_SAMCTX) { *nargs = 5; *ptr_mask = 0x08; }           // J, nctx, agg_alpha, y, ldy
 }
 size_t struct_size(int fn) {
@@ -91,6 +93,7 @@ size_t struct_size(int fn) {
     case F_SAMCTX: return sizeof(dh_sam_args);
     case F_DWS: return sizeof(dh_dw_strided);
     case F_CONVT: return sizeof(dh_conv_transpose);
+    case F_CONVTS: return sizeof(dh_conv_transpose);
   }
   return 0;
 }
@@ -140,6 +143,12 @@ int run_step(const Step& st, void* stream) {
       std::memcpy(&cfg, p + sizeof(dh_conv_transpose), 8);
       return dh_conv2d_transpose2x2_f32(reinterpret_cast<const dh_conv_transpose*>(p), (int)cfg, stream);
     }
+    case F_CONVTS: {
+      int64_t parts, cfg;
+      std::memcpy(&parts, p + sizeof(dh_conv_transpose), 8);
+      std::memcpy(&cfg, p + sizeof(dh_conv_transpose) + 8, 8);
+      return dh_conv2d_transpose2x2_split_f32(reinterpret_cast<const dh_conv_transpose*>(p), (int)parts, (int)cfg, stream);
+    }
     case F_GROUP:
       return dh_conv2d_dw_group_f32(reinterpret_cast<const dh_conv_args*>(p),
                                     reinterpret_cast<const dh_dw_args*>(p + sizeof(dh_conv_args)), stream);
@@ -178,7 +187,8 @@ int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
   r.p += 4;
   const uint32_t version = r.get<uint32_t>();
   // version 3 = version 2 + the step records of dh_dwconv2d_strided_f32 / dh_conv2d_transpose2x2_f32 (function ids 19, 20)
-  if (version < 1 || version > 3) return DH_EINVAL;
+  // version 4 = version 3 + the step record of dh_conv2d_transpose2x2_split_f32 (function id 21)
+  if (version < 1 || version > 4) return DH_EINVAL;
   dh_plan* pl = new dh_plan();
   pl->n = r.get<int32_t>();
   pl->arena_bytes = r.get<uint64_t>();
@@ -210,7 +220,7 @@ int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
     Step st;
     st.fn = (int)r.get<uint32_t>();
     const uint32_t nb = r.get<uint32_t>();
-    if (!r.ok || st.fn < 0 || st.fn >= (version >= 3 ? (int)F_COUNT : (int)F_DWS) || r.p + nb > r.end) return fail(DH_EINVAL);
+    if (!r.ok || st.fn < 0 || st.fn >= (version >= 4 ? (int)F_COUNT : (version == 3 ? (int)F_CONVTS : (int)F_DWS)) || r.p + nb > r.end) return fail(DH_EINVAL);
     st.payload.assign(r.p, r.p + nb);
     r.p += nb;
     pl->steps.push_back(std::move(st));

@@ -65,13 +65,14 @@ class WeightStore:
 
     CONVT = 'convt'       # packing key of a Conv2DTranspose kernel in `conv` (beside the dh_conv_args.w_split codes)
 
-    def convt_weight(self, p):
+    def convt_weight(self, p, split=0):
         """Keras Conv2DTranspose kernel [2, 2, Cout, Cin] as the packed [Cin, 4 * Cout] B operand of the depth-to-space
-        GEMM (packing.pack_convt); kept in `conv` like every packed GEMM weight."""
-        key = (id(p), self.CONVT)
+        GEMM (packing.pack_convt); kept in `conv` like every packed GEMM weight.  split = 0: fp32; 1 / 3 / 4 (the codes of
+        dh_conv_args.w_split): the split-bf16 packing with three / two / one part, kept beside the fp32 one."""
+        key = (id(p), self.CONVT if not split else (self.CONVT, int(split)))
         ent = self.conv.get(key)
         if ent is None or ent[3] != p.version:
-            packed, kp, np_ = packing.pack_convt(self._require(p))
+            packed, kp, np_ = packing.pack_convt(self._require(p), parts=packing.SPLIT_PARTS[int(split)] if split else None)
             if ent is None:
                 ent = (self._dev(packed), kp, np_, p.version)
             else:
@@ -329,10 +330,9 @@ class BoundPlan:
             self._keep.append(args)
             self.calls.append((lib.dh_dwconv2d_strided_f32, (C.byref(args),), s))
         elif k == 'convtranspose':
-            x, y = s.ins['x'], s.outs['y']             # Conv2DTranspose((2, 2), strides=(2, 2)): always the fp32 path,
-            args = _lib.ConvtArgs()                    # whatever plan.gemm_precision says
-            wt, kp, np_ = self.store.convt_weight(s.params['w'])
-            args.x, args.w, args.y = P(x), wt.data_ptr(), P(y)
+            x, y = s.ins['x'], s.outs['y']             # Conv2DTranspose((2, 2), strides=(2, 2))
+            args = _lib.ConvtArgs()
+            args.x, args.y = P(x), P(y)
             if 'pre_bn' in s.params:
                 sc, sh = self.store.bn_affine(s.params['pre_bn'])
                 args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
@@ -340,10 +340,25 @@ class BoundPlan:
             if r1 is not None:
                 args.res, args.ldr = P(r1), r1.ld
             args.N, args.H, args.W, args.Cin, args.ldx = n * x.lead(3), x.shape[-3], x.shape[-2], x.C, x.ld
-            args.Cout, args.ldy, args.Kp, args.Np = a['Cout'], y.ld, kp, np_
+            kp_np = (C.c_int(), C.c_int())
+            _lib.check(lib.dh_conv2d_packed_dims(1, 1, x.C, 4 * a['Cout'], C.byref(kp_np[0]), C.byref(kp_np[1])))
+            args.Cout, args.ldy, args.Kp, args.Np = a['Cout'], y.ld, kp_np[0].value, kp_np[1].value
             args.pre_relu, args.post_relu = a['pre_relu'], a['post_relu']
+            # plan.gemm_precision: the split-bf16 form when the library takes the layer (one rule for the three modes, asked
+            # with the final argument struct BEFORE the weights are packed, as weight_layout does for convolutions)
+            split = SPLIT_CODES.get(getattr(self.plan, 'gemm_precision', 'f32'), 0)
+            if split and not lib.dh_conv2d_transpose2x2_split_eligible(C.byref(args)):
+                split = 0
+            wt, kp, np_ = self.store.convt_weight(s.params['w'], split=split)
+            assert (kp, np_) == (args.Kp, args.Np)
+            args.w = wt.data_ptr()
+            a['w_split'] = int(split)                  # 1 / 3 / 4 as for convolutions, 0: the fp32 kernel
             self._keep.append(args)
-            self.calls.append((lib.dh_conv2d_transpose2x2_f32, (C.byref(args), a.get('tile_cfg', -1)), s))
+            if split:
+                self.calls.append((lib.dh_conv2d_transpose2x2_split_f32,
+                                   (C.byref(args), packing.SPLIT_PARTS[split], a.get('tile_cfg', -1)), s))
+            else:
+                self.calls.append((lib.dh_conv2d_transpose2x2_f32, (C.byref(args), a.get('tile_cfg', -1)), s))
         elif k == 'dwconv':
             x, y = s.ins['x'], s.outs['y']
             args = _lib.DwArgs()
@@ -969,8 +984,9 @@ class Executor:
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             for s in self.plan.steps:
                 for role, p in s.params.items():
-                    if role == 'w' and s.kind == 'convtranspose':
-                        self.store.convt_weight(p)
+                    if role == 'w' and s.kind == 'convtranspose':   # every packing in use: fp32 and / or the modes'
+                        for (pid, key) in [k_ for k_ in self.store.conv if k_[0] == id(p)]:
+                            self.store.convt_weight(p, split=key[1] if isinstance(key, tuple) else 0)
                     elif role == 'w' and s.kind != 'dwconv':
                         for (pid, split) in [k_ for k_ in self.store.conv if k_[0] == id(p)]:
                             self.store.conv_weight(p, split=split)

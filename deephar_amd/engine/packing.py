@@ -29,10 +29,14 @@ def convt_matrix(w):
     return np.ascontiguousarray(w.transpose(3, 0, 1, 2)).reshape(1, 1, cin, 4 * cout)
 
 
-def pack_convt(w):
+def pack_convt(w, parts=None):
     """Keras Conv2DTranspose kernel [2, 2, Cout, Cin] -> ([Kp/4][Np][4] float32, Kp, Np): the [Cin, 4 * Cout] B operand
-    through the pointwise packer; the four column blocks are contiguous, the padding to Np follows the last one."""
-    return pack_conv(convt_matrix(w))
+    through the pointwise packer; the four column blocks are contiguous, the padding to Np follows the last one.
+    parts = 3 / 2 / 1: the same matrix through the split-bf16 packer (pack_conv_split: [Kp/8][parts][Np][8] bf16, as a
+    float32-typed array) for dh_conv2d_transpose2x2_split_f32; None: the fp32 packing."""
+    if parts is None:
+        return pack_conv(convt_matrix(w))
+    return pack_conv_split(convt_matrix(w), parts=parts)
 
 
 HALO_CHUNK = 16      # channels per resident chunk of csrc/conv_halo.hip

@@ -3,7 +3,9 @@ dh_plan_destroy -- SURVEY.md 8b's plan / execute pair): a host written in C or C
 
 Blob (little endian), version 2 (version 1 = float inputs only, no `u8 bytes` / `dtype`, still read by the library);
 a plan with a strided depthwise or a transposed-convolution step (downsampling_type='conv') is written as version 3: the
-same layout with the two further function ids -- every other plan stays version 2, byte for byte what it was:
+same layout with the two further function ids -- every other plan stays version 2, byte for byte what it was; a plan with
+a split-bf16 transposed convolution (downsampling_type='conv' under a gemm_precision other than 'f32') is version 4, again
+the same layout with one more function id (V4_FUNCTIONS) -- every other plan keeps its version 2 or 3:
     header   'DHPL' u32 version | i32 batch n | u64 arena bytes | u64 weight bytes | u32 #inputs | u32 #outputs | u32 #steps
              | u64 u8 bytes (size of region 3: the byte staging buffers of a uint8-input plan, 0 otherwise)
     inputs   per input : u64 tagged pointer of the buffer dh_forward copies the caller's data into (region 1: the plan's
@@ -33,6 +35,9 @@ FUNCTIONS = ['dh_conv2d_f32', 'dh_dwconv2d_f32', 'dh_pool2d_f32', 'dh_upsample2x
              'dh_depth_from_maps_f32', 'dh_softargmax2d_context_f32', 'dh_normalize_u8_f32', 'dh_conv2d_dw_group_f32',
              'dh_conv2d_pair_f32', 'dh_conv2d_seg_f32', 'dh_dwconv2d_strided_f32', 'dh_conv2d_transpose2x2_f32']
 V3_FUNCTIONS = FUNCTIONS.index('dh_dwconv2d_strided_f32')     # function ids from here on make a blob version 3
+# appended behind FUNCTIONS (the ids of versions 1 - 3 do not move): function ids from len(FUNCTIONS) on make a blob version 4
+V4_FUNCTIONS = ['dh_conv2d_transpose2x2_split_f32']
+ALL_FUNCTIONS = FUNCTIONS + V4_FUNCTIONS
 ARENA, WEIGHTS, BYTES = 1, 2, 3
 
 
@@ -93,6 +98,12 @@ def _scalars(sig, args, reg):
     return b''.join(parts)
 
 
+def blob_version(function_ids):
+    """The blob version a plan with these step function ids is written as: the lowest that knows them all."""
+    top = max(function_ids, default=0)
+    return 4 if top >= len(FUNCTIONS) else (3 if top >= V3_FUNCTIONS else VERSION)
+
+
 def dump_plan(model, batch, u8_norm=None):
     """-> bytes.  `model`'s plan bound (and autotuned) for `batch`; needs a HIP device (the weight image is read back).
     u8_norm: None for float inputs; a channel_power (as for Executor.bind) for a plan that takes raw uint8 frames and
@@ -105,8 +116,8 @@ def dump_plan(model, batch, u8_norm=None):
         bp = ex.bind(batch, u8_norm=u8_norm)
     ex.stream.synchronize()
     lib = _lib.load()
-    names = {n: i for i, n in enumerate(FUNCTIONS)}
-    by_addr = {C.cast(getattr(lib, n), C.c_void_p).value: n for n in FUNCTIONS}
+    names = {n: i for i, n in enumerate(ALL_FUNCTIONS)}
+    by_addr = {C.cast(getattr(lib, n), C.c_void_p).value: n for n in ALL_FUNCTIONS}
     reg = _Regions(bp)
     steps = []
     for idx, (fn, args, step) in enumerate(bp.calls):
@@ -133,7 +144,7 @@ def dump_plan(model, batch, u8_norm=None):
             payload = _scalars(sig, args, reg)
         steps.append(struct.pack('<II', names[name], len(payload)) + payload)
     plan = bp.plan
-    version = 3 if any(struct.unpack_from('<I', st)[0] >= V3_FUNCTIONS for st in steps) else VERSION
+    version = blob_version(struct.unpack_from('<I', st)[0] for st in steps)
     head = MAGIC + struct.pack('<IiQQIIIQ', version, bp.n, bp.arena.numel() * 4, (reg.size + 255) & ~255,
                                len(plan.inputs), len(plan.outputs), len(steps), reg.u8_size)
     ins = b''

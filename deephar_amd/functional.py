@@ -185,19 +185,26 @@ def dwconv2d_strided(x, dw_kernel, strides=(2, 2), pre_scale=None, pre_shift=Non
     return y
 
 
-def pack_convt_weight(w, device='cuda'):
-    """Keras Conv2DTranspose kernel [2,2,Cout,Cin] (numpy) -> (packed device tensor, Kp, Np) for conv2d_transpose."""
+def pack_convt_weight(w, device='cuda', parts=None):
+    """Keras Conv2DTranspose kernel [2,2,Cout,Cin] (numpy) -> (packed device tensor, Kp, Np) for conv2d_transpose.
+    parts = 3 / 2 / 1: the split-bf16 packing of precision = 'bf16x3' / 'bf16x2' / 'bf16'; None: fp32."""
     torch = _t()
-    packed, kp, np_ = packing.pack_convt(np.asarray(w, np.float32))
+    packed, kp, np_ = packing.pack_convt(np.asarray(w, np.float32), parts=parts)
     return torch.from_numpy(packed).to(device), kp, np_
 
 
 def conv2d_transpose(x, w, strides=(2, 2), pre_scale=None, pre_shift=None, pre_relu=False, res=None, post_relu=False,
-                     tile_cfg=-1, packed=None, channels=None, out=None):
+                     tile_cfg=-1, packed=None, channels=None, out=None, precision=None):
     """Conv2DTranspose((2, 2), strides=(2, 2), use_bias=False) with the fused BN / ReLU prologue and residual / ReLU
     epilogue of dh_conv2d_transpose2x2_f32.  x [N,H,W,Cin]; w numpy, Keras layout [2,2,Cout,Cin]; res [N,2H,2W,ldr] at the
     OUTPUT resolution.  channels: x is [N,H,W,ldx] and only its first Cin channels are read; out: a preallocated
-    [N,2H,2W,ldy] tensor whose first Cout channels are written.  Always fp32 (no gemm_precision applies)."""
+    [N,2H,2W,ldy] tensor whose first Cout channels are written.
+    precision: None / 'f32' (fp32 matrix path), or 'bf16x3' / 'bf16x2' / 'bf16' -- the split-bf16 form with three / two / one
+    bf16 part per operand (dh_conv2d_transpose2x2_split_f32; tile_cfg then indexes its tilings).  A `packed` weight must have
+    been packed for the same mode (pack_convt_weight(..., parts=...))."""
+    if precision not in (None, 'f32', 'bf16x3', 'bf16x2', 'bf16'):
+        raise ValueError("precision must be 'f32', 'bf16x3', 'bf16x2' or 'bf16', got %r" % (precision,))
+    parts = {None: None, 'f32': None, 'bf16x3': 3, 'bf16x2': 2, 'bf16': 1}[precision]
     torch = _t()
     kh, kw, cout, cin = w.shape
     if (kh, kw) != (2, 2) or tuple(strides) != (2, 2):
@@ -206,7 +213,7 @@ def conv2d_transpose(x, w, strides=(2, 2), pre_scale=None, pre_shift=None, pre_r
     lib = _lib.load()
     n, h, w_, ldx = x.shape
     assert (channels or ldx) == cin
-    wt, kp, np_ = packed if packed is not None else pack_convt_weight(w, x.device)
+    wt, kp, np_ = packed if packed is not None else pack_convt_weight(w, x.device, parts=parts)
     y = out if out is not None else torch.empty((n, 2 * h, 2 * w_, cout), dtype=torch.float32, device=x.device)
     assert tuple(y.shape[:3]) == (n, 2 * h, 2 * w_) and y.shape[3] >= cout
     a = _lib.ConvtArgs()
@@ -214,6 +221,10 @@ def conv2d_transpose(x, w, strides=(2, 2), pre_scale=None, pre_shift=None, pre_r
     a.N, a.H, a.W, a.Cin, a.ldx = n, h, w_, cin, ldx
     a.Cout, a.ldy, a.ldr = cout, y.shape[3], res.shape[-1] if res is not None else 0
     a.Kp, a.Np, a.pre_relu, a.post_relu = kp, np_, int(pre_relu), int(post_relu)
+    if parts is not None:
+        _lib.check(lib.dh_conv2d_transpose2x2_split_f32(C.byref(a), parts, tile_cfg, _stream()),
+                   'dh_conv2d_transpose2x2_split_f32')
+        return y
     _lib.check(lib.dh_conv2d_transpose2x2_f32(C.byref(a), tile_cfg, _stream()), 'dh_conv2d_transpose2x2_f32')
     return y
 

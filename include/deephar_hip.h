@@ -226,8 +226,9 @@ int dh_dwconv2d_strided_f32(const dh_dw_strided* a, void* stream);
  * 1, 1, Cin, 4 * Cout); Kp / Np are dh_conv2d_packed_dims(1, 1, Cin, 4 * Cout).  The four column blocks are contiguous
  * (the padding to Np follows the last one); the kernel finds a column's block by comparison, for any Cout.
  * K is summed ascending in every tiling: result bits depend on neither tile_cfg (< 0: library heuristic, else
- * 0 .. dh_conv2d_transpose2x2_num_tile_cfgs() - 1) nor batch size.  This layer has no reduced-precision form: under every
- * gemm_precision of the engine it stays fp32 (4 % of the FLOPs of a two-pyramid SPNet at 256 px, 11 % of an eight-pyramid one).
+ * 0 .. dh_conv2d_transpose2x2_num_tile_cfgs() - 1) nor batch size.  The reduced-precision forms of the layer (the engine's
+ * gemm_precision = 'bf16x3' / 'bf16x2' / 'bf16') are dh_conv2d_transpose2x2_split_f32 below; the layer is 4 % of the FLOPs of
+ * a two-pyramid SPNet at 256 px, 11 % of an eight-pyramid one.
  * Needs Cin % 4 == 0, ldx % 4 == 0, 16-byte aligned x (DH_EUNSUPPORTED otherwise); inputs must be finite (see dh_conv2d_f32).
  * Other transposed-convolution geometries are not built.
  * ------------------------------------------------------------------------------------------------- */
@@ -245,6 +246,28 @@ typedef struct dh_conv_transpose {
 } dh_conv_transpose;
 int dh_conv2d_transpose2x2_num_tile_cfgs(void);
 int dh_conv2d_transpose2x2_f32(const dh_conv_transpose* a, int tile_cfg, void* stream);
+/* The same layer on the split-bf16 precision ladder (csrc/convt2x2s.hip): `parts` = 3 / 2 / 1 bf16 parts per operand
+ * ("bf16x3" / "bf16x2" / "bf16", the modes of dh_conv_args.w_split = 1 / 3 / 4); any other value is DH_EINVAL.  `a` as for
+ * dh_conv2d_transpose2x2_f32 except a->w: the same matrix B[ci][(2a + b) * Cout + co] packed by
+ * dh_conv2d_pack_weights_parts_host(B, ., 1, 1, Cin, 4 * Cout, parts) as [Kp/8][parts][Np][8] bf16.
+ *   operand  a[m, k] = relu?( fmaf(x[m, k], pre_scale[k], pre_shift[k]) ) in fp32 -- the ONE fused multiply-add of the fp32
+ *            kernel, so the operand has its bits (a[m, k] = relu?(x[m, k]) without a prologue) -- then split by repeated
+ *            round-to-nearest-even into `parts` bf16 parts: the split follows the prologue and the ReLU;
+ *   sum      E_P = sum_k sum_{i + j <= parts + 1} a_i[k] b_j[k], products exact, fp32 accumulation, smallest product first
+ *            per 16 k, K ascending in every tiling;
+ *   store    the depth-to-space epilogue of the fp32 kernel, unchanged: residual at the output resolution, then ReLU.
+ * Result bits depend on `parts` and the layer's geometry only: not on tile_cfg (< 0: library heuristic, else
+ * 0 .. dh_conv2d_transpose2x2_num_split_tile_cfgs() - 1), batch size, position in the batch, or the vector / scalar store
+ * path.  NOT bit-identical to dh_conv2d_transpose2x2_f32.  A layer dh_conv2d_transpose2x2_split_eligible refuses answers
+ * DH_EUNSUPPORTED.  Inputs must be finite (see dh_conv2d_f32: a padded k slot holds the next pixel's floats, here times a
+ * zero scale or a zero weight). */
+int dh_conv2d_transpose2x2_num_split_tile_cfgs(void);
+/* 1 when dh_conv2d_transpose2x2_split_f32 accepts this layer -- ONE rule for the three modes, on geometry and alignment only
+ * (never on batch size or timing; every field but `w` filled in as for the launch, no pointer is dereferenced): Cin % 4 == 0,
+ * ldx % 4 == 0, 16-byte aligned x, operands within the 32-bit buffer offsets of the kernel, and with a BatchNormalization
+ * prologue Kp <= 4096 (its scale / shift tables live in LDS).  A binding asks this BEFORE it packs the weights. */
+int dh_conv2d_transpose2x2_split_eligible(const dh_conv_transpose* a);
+int dh_conv2d_transpose2x2_split_f32(const dh_conv_transpose* a, int parts, int tile_cfg, void* stream);
 
 /* [r06] The two independent first layers of a pre-activation residual unit in ONE launch (deephar/models/common.py:25-67:
  * `shortcut = conv2d(relu(BN(x)), out, (1, 1))` beside `sepconv2d(relu(BN(x)), ...)`, whose depthwise half is `dw`): the
