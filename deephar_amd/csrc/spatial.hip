@@ -469,6 +469,7 @@ int launch_upsample2x_add(const float* a, int lda, const float* b, int ldb, floa
 int launch_eltwise(const EltArgs& a, hipStream_t s) {
   if (a.npix <= 0 || a.C <= 0 || a.a == nullptr || a.y == nullptr) return DH_EINVAL;
   if (a.op == 1 && a.b == nullptr) return DH_EINVAL;
+  if (a.scale != nullptr && a.shift == nullptr) return DH_EINVAL;   // the affine reads both tables
   hipLaunchKernelGGL(eltwise_kernel, dim3(grid_for(a.npix * a.C)), dim3(256), 0, s, a);
   return check_launch();
 }

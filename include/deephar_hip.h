@@ -323,7 +323,8 @@ int dh_upsample2x_add_f32(const float* a, int lda, const float* b, int ldb, floa
 
 /* element-wise glue: keras add / multiply / Activation('sigmoid') / standalone BatchNormalization+ReLU.
  *   op 0: y = relu?( (a*scale+shift) + b + c )    op 1: y = (a*scale+shift) * b
- *   op 2: y = sigmoid( (a*scale+shift) + b )      bcast_b: b has one channel, broadcast over C */
+ *   op 2: y = sigmoid( (a*scale+shift) + b )      bcast_b: b has one channel, broadcast over C
+ * scale and shift are [C] tables given together or not at all: scale without shift is DH_EINVAL (shift alone is ignored). */
 typedef struct dh_elt_args {
   const float* a;
   const float* b;

@@ -1,0 +1,116 @@
+"""Channel-slab views for the op-level tests.  TEST INFRASTRUCTURE (a plain module, imported like tests/wellcond.py).
+
+The planner hands nearly every kernel a (pointer, pitch) view: a run of C channels at offset `off` inside pixels of `ld`
+floats (concatenation slabs, pose-buffer columns, pooled / concatenated runs sharing a buffer).  `slab` builds such a view
+on the device, `assert_untouched` checks bit for bit that a launch wrote nothing outside it:
+
+  * inputs are built with fill = NaN, so a read outside the view that reaches a result poisons it;
+  * outputs are built with a finite canary everywhere (inside the view too: an element the kernel forgets keeps it);
+  * every slab sits between two guard runs of GUARD floats holding the same fill, so that an overrun in front of the
+    first or behind the last pixel shows as well -- also for the dense layout, where the tensor itself has no spare channel.
+
+Three layouts are used throughout (`layout`):
+  dense    ld = C, off = 0
+  aligned  ld a multiple of 4 above C, off a multiple of 4: the float4 path of a kernel, with a pitch
+  odd      an odd off (and an odd ld unless the caller needs another): the scalar path
+`k` = 0, 1, 2 .. gives the operands of one launch different pitches and offsets.
+
+Also here, because the GPU test and the host test share it: the shapes that reach the four instantiations of the 2-D
+soft-argmax kernel, and the launcher's variant choice restated (`sam_variant`).
+"""
+import numpy as np
+
+CANARY = 7.0
+GUARD = 64            # floats in front of and behind every slab: 256 bytes, keeps the slab's 16-byte alignment
+LAYOUTS = ('dense', 'aligned', 'odd')
+
+
+def layout(C, name, k=0):
+    """(ld, off) of layout `name` for a C-channel view; operand number k of a launch."""
+    if name == 'dense':
+        return C, 0
+    if name == 'aligned':
+        return (C + 3) // 4 * 4 + 4 * (2 + k), 4 * (1 + k)
+    if name == 'odd':
+        off = 1 + 2 * k
+        return (C + off + 2 * k + 1) | 1, off
+    raise ValueError(name)
+
+
+def slab(values, ld, off, fill, device='cuda'):
+    """Put a [..., C] array into channels [off, off + C) of a [..., ld] float32 device tensor whose other channels (and the
+    guard runs around it) hold `fill`.  Returns (tensor, device pointer of the view = data_ptr() + 4 * off)."""
+    import torch
+    v = np.asarray(values, np.float32)
+    C = v.shape[-1]
+    assert 0 <= off and off + C <= ld, (C, ld, off)
+    buf = np.full(v.shape[:-1] + (ld,), fill, np.float32)
+    buf[..., off:off + C] = v
+    flat = np.full(buf.size + 2 * GUARD, fill, np.float32)
+    flat[GUARD:GUARD + buf.size] = buf.ravel()
+    base = torch.from_numpy(flat).to(device)
+    t = base[GUARD:GUARD + buf.size].view(buf.shape)
+    assert t._base is base and t.data_ptr() % 16 == 0
+    return t, t.data_ptr() + 4 * off
+
+
+def out_slab(shape, ld, off, canary=CANARY, device='cuda'):
+    """An output view of `shape` = [..., C]: the whole slab, the view included, holds the canary."""
+    return slab(np.full(shape, canary, np.float32), ld, off, canary, device)
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().numpy().view(np.uint32)
+
+
+def assert_untouched(tensor, off, C, canary=CANARY, what=''):
+    """Everything outside channels [off, off + C) of a tensor made by `slab`, guard runs included, still holds `canary`
+    bit for bit."""
+    want = np.array(canary, np.float32).view(np.uint32)
+    b = _bits(tensor)
+    assert np.all(b[..., :off] == want) and np.all(b[..., off + C:] == want), \
+        '%s: wrote outside channels [%d, %d) of its %d-float pixels' % (what, off, off + C, tensor.shape[-1])
+    g = _bits(tensor._base)
+    assert np.all(g[:GUARD] == want), '%s: wrote in front of its buffer' % what
+    assert np.all(g[-GUARD:] == want), '%s: wrote behind its buffer' % what
+
+
+def view(tensor, off, C):
+    """The view's values as a NumPy array [..., C]."""
+    return tensor[..., off:off + C].detach().cpu().contiguous().numpy()
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+# ---- the 2-D soft-argmax launcher's variant choice (csrc/decoder.hip: launch_softargmax2d), restated ------------------
+SAM_WIDE_BLOCKS = 1024             # `blocks16 >= 1024`: 16 channels per work-group once F * ceil(C / 16) fills the chip
+SAM_SLAB_WIDE = 128 * 1024         # bytes of LDS above which the 16-channel kernel reads the maps from memory
+SAM_SLAB_NARROW = 60 * 1024        # the same for the 4-channel kernel
+# the statements of the launcher the three numbers restate, as they stand in the source
+SAM_SOURCE_LINES = ('const bool wide = blocks16 >= 1024;',
+                    'constexpr size_t kMaxSlab = 128 * 1024;',
+                    'if (slab > (wide ? kMaxSlab : (size_t)60 * 1024)) {')
+
+
+def sam_slab_bytes(H, W, g):
+    return (H * W * g + W + H) * 4
+
+
+def sam_variant(F, H, W, C):
+    """(channels per work-group, staged in LDS) of softargmax2d_kernel<G, STAGED> for an [F, H, W, C] launch."""
+    wide = F * ((C + 15) // 16) >= SAM_WIDE_BLOCKS
+    g = 16 if wide else 4
+    return g, sam_slab_bytes(H, W, g) <= (SAM_SLAB_WIDE if wide else SAM_SLAB_NARROW)
+
+
+# (F, H, W, C) -> the instantiation the shape is there for
+SAM_VARIANT_SHAPES = {
+    (1024, 4, 4, 16): (16, True),
+    (512, 8, 8, 17): (16, True),       # the second channel group holds one live channel
+    (1024, 46, 46, 3): (16, False),    # slab of 135 792 B
+    (2, 64, 64, 5): (4, False),        # slab of 66 048 B
+    (3, 16, 16, 17): (4, True),        # the shape of the view cases
+}
