@@ -131,7 +131,9 @@ int dh_conv2d_num_split_tile_cfgs(void); /* tilings of the w_split = 1 / 3 / 4 k
                                             a tiling a mode does not have answers DH_EUNSUPPORTED */
 int dh_conv2d_pick_tile_cfg(int M, int Cout);
 /* Inputs must be FINITE.  K is padded to the kernels' step with zero weights, and on the LDS-DMA GEMM a padded k slot of
- * a pixel holds the following floats in memory (the next pixel's first channels, clamped inside the buffer): an Inf / NaN
+ * a pixel holds the following floats in memory (the next pixel's first channels, clamped inside the buffer; on a view with
+ * ldx > Cin the channels BEHIND the view inside the same pixel, i.e. the neighbouring tensor of a shared slab -- which is why
+ * planner rule R4b keeps convolutions out of _VIEW_READERS): an Inf / NaN
  * there would reach this pixel's output as 0 * Inf.  The first-layer kernel (raw frames) and the skinny-conv
  * kernel zero the padded A operand instead; activations inside a model are finite by construction. */
 /* 1 when dh_conv2d_f32 runs this convolution on the skinny-conv kernel (conv_splitk.hip: a tiny output map -- at most 256

@@ -31,12 +31,14 @@ def test_softargmax2d_shapes_reach_all_four_instantiations():
 def test_slab_layouts_are_what_they_claim():
     """dense / aligned / odd for every channel count and operand number the GPU tests use: the view fits its pixel, the
     aligned layout keeps 16-byte alignment with a pitch, the odd one breaks it."""
-    for C in (1, 2, 3, 5, 16, 17, 20, 24, 60, 300, 576):
-        for k in range(3):
+    # (second row: the channel counts of tests/convview.py, whose launches have up to five operands)
+    for C in (1, 2, 3, 5, 16, 17, 20, 24, 60, 300, 576,
+              18, 30, 32, 40, 48, 64, 66, 70, 72, 94, 96, 100, 200, 264):
+        for k in range(5):
             assert SV.layout(C, 'dense', k) == (C, 0)
             ld, off = SV.layout(C, 'aligned', k)
             assert ld % 4 == 0 and off % 4 == 0 and off > 0 and off + C <= ld and ld > C
             ld, off = SV.layout(C, 'odd', k)
             assert ld % 2 == 1 and off % 2 == 1 and off + C <= ld
-        assert len({SV.layout(C, 'aligned', k) for k in range(3)}) == 3
-        assert len({SV.layout(C, 'odd', k) for k in range(3)}) == 3
+        assert len({SV.layout(C, 'aligned', k) for k in range(5)}) == 5
+        assert len({SV.layout(C, 'odd', k) for k in range(5)}) == 5
