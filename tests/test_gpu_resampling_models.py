@@ -25,25 +25,7 @@ def _all_off():
 
 
 # ---- 9. mini pyramid ------------------------------------------------------------------------------------------------------
-MINI_LAYERS = 9      # GEMM / depthwise layers on the longest path: 3 x (depthwise + pointwise) down, 3 transposed convs up
-
-
-def _mini_pyramid():
-    from deephar_amd import Model, graph, layers as L, utils, weights
-    from deephar_amd.config import ModelConfig
-    from deephar_amd.models.common import downscaling_unit, upscaling_unit
-    graph.reset_naming()
-    cfg = ModelConfig((16, 16, 96), utils.pa16j2d, kernel_size=(5, 5), growth=32, downsampling_type='conv')
-    x = L.Input((16, 16, 96))
-    xs = [x]
-    for i in (1, 2, 3):
-        xs.append(downscaling_unit(xs[-1], cfg, out_size=xs[-1].shape[-1] + cfg.growth, name='du%d' % i))
-    y = xs[-1]
-    for i in (2, 1, 0):
-        y = L.add([upscaling_unit(y, cfg, out_size=y.shape[-1] - cfg.growth, name='uu%d' % i), xs[i]])
-    m = Model(x, y, name='mini_pyramid')
-    weights.init_synthetic(m, seed=0)
-    return m, weights.as_dict(m)
+MINI_LAYERS, _mini_pyramid = R.MINI_LAYERS, R.build_mini_pyramid      # (shared with the host tests)
 
 
 @pytest.fixture(scope='module')
