@@ -74,6 +74,7 @@ SIGNATURES = {
     'dh_conv2d_uses_split_k': (C.c_int, [C.POINTER(ConvArgs)]),
     'dh_conv2d_uses_first_layer_kernel': (C.c_int, [C.POINTER(ConvArgs)]),
     'dh_conv2d_split_eligible': (C.c_int, [C.POINTER(ConvArgs)]),
+    'dh_conv2d_split_wide_eligible': (C.c_int, [C.POINTER(ConvArgs)]),
     'dh_conv2d_halo_eligible': (C.c_int, [C.POINTER(ConvArgs)]),
     'dh_conv2d_num_halo_tile_cfgs': (C.c_int, []),
     'dh_conv2d_f32': (C.c_int, [C.POINTER(ConvArgs), C.c_int, vp]),

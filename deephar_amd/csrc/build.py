@@ -13,13 +13,15 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
-SOURCES = ["conv_igemm.hip", "gemm1x1.hip", "convt2x2.hip", "convt2x2s.hip", "gemm1x1s.hip", "gemm1x1s_p2.hip", "gemm1x1s_p1.hip", "conv_splitk.hip", "conv_halo.hip", "conv_stem.hip", "spatial.hip", "decoder.hip",
+SOURCES = ["conv_igemm.hip", "gemm1x1.hip", "convt2x2.hip", "convt2x2s.hip", "gemm1x1s.hip", "gemm1x1s_p2.hip", "gemm1x1s_p1.hip",
+           "gemm1x1s_ext.hip", "gemm1x1s_ext_p2.hip", "gemm1x1s_ext_p1.hip", "conv_splitk.hip", "conv_halo.hip", "conv_stem.hip", "spatial.hip", "decoder.hip",
            "capi.hip", "plan.hip"]
 HEADERS = [os.path.join(HERE, "dh_kernels.h"), os.path.join(HERE, "conv_common.h"), os.path.join(HERE, "dw_lds.h"),
            os.path.join(HERE, "gemm1x1s_body.h"),
            os.path.join(INCLUDE, "deephar_hip.h")]
 INCLUDES = {"gemm1x1s_p2.hip": ["gemm1x1s.hip"], "gemm1x1s_p1.hip": ["gemm1x1s.hip"], "convt2x2.hip": ["gemm1x1.hip"],
-            "convt2x2s.hip": ["gemm1x1s.hip"]}   # sources that include a source
+            "convt2x2s.hip": ["gemm1x1s.hip"], "gemm1x1s_ext.hip": ["gemm1x1s.hip"],
+            "gemm1x1s_ext_p2.hip": ["gemm1x1s.hip", "gemm1x1s_ext.hip"], "gemm1x1s_ext_p1.hip": ["gemm1x1s.hip", "gemm1x1s_ext.hip"]}   # sources that include a source
 LIB = os.path.join(HERE, "libdeephar_hip.so")
 OBJDIR = os.path.join(HERE, "build")
 ARCH = "gfx950"

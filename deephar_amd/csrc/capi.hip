@@ -111,6 +111,7 @@ int dh_conv2d_uses_first_layer_kernel(const dh_conv_args* a) {
 }
 int dh_conv2d_pick_tile_cfg(int M, int Cout) { return conv_igemm_pick_cfg(M, Cout); }
 int dh_conv2d_split_eligible(const dh_conv_args* a) { return a != nullptr && gemm1x1_split_eligible(*a) ? 1 : 0; }
+int dh_conv2d_split_wide_eligible(const dh_conv_args* a) { return a != nullptr && gemm1x1_split_wide_eligible(*a) ? 1 : 0; }
 int dh_conv2d_halo_eligible(const dh_conv_args* a) { return a != nullptr && conv_halo_eligible(*a) ? 1 : 0; }
 int dh_conv2d_num_halo_tile_cfgs(void) { return conv_halo_num_cfgs(); }
 

@@ -277,6 +277,7 @@ int launch_cfg(const ConvArgs& a, bool vec4, int epi, hipStream_t s) {
 bool gemm1x1_eligible(const ConvArgs& a);
 int launch_gemm1x1(const ConvArgs& a, int cfg, int epi, hipStream_t s);
 int launch_gemm1x1_split(const ConvArgs& a, int cfg, int epi, hipStream_t s);
+int launch_gemm1x1_split_wide(const ConvArgs& a, int cfg, int epi, hipStream_t s);
 int gemm1x1_split_num_cfgs();
 int gemm1x1_num_cfgs();
 bool conv_is_skinny(const ConvArgs& a);
@@ -311,7 +312,7 @@ int launch_conv_igemm(const ConvArgs& a, int cfg, hipStream_t s) {
   if ((long long)a.N * a.H * a.W > 0x7fffffffLL || (long long)a.N * a.OH * a.OW * (a.up2 ? 4 : 1) > 0x7fffffffLL)
     return DH_EINVAL;
   if (a.x_u8 && a.in_lut == nullptr) return DH_EINVAL;
-  if (a.w_split < 0 || a.w_split > 4) return DH_EINVAL;
+  if (a.w_split < 0 || a.w_split > 7) return DH_EINVAL;
   // tiny output, long reduction: the in-work-group split-K kernel, whatever tiling was asked for (shape rule: the
   // result bits of a layer must not depend on a timing-based choice)
   if (a.y_pool != nullptr) {             // pooled second output: one image row per wave (pairs of waves pool), or [r06] two /
@@ -347,6 +348,10 @@ int launch_conv_igemm(const ConvArgs& a, int cfg, hipStream_t s) {
     cfg = conv_igemm_pick_cfg(a.N * a.OH * a.OW, a.Cout) + (!a.w_split && !a.x_u8 && gemm1x1_eligible(a) ? kNumCfgs : 0);
   if (!a.w_split && cfg >= kNumCfgs + gemm1x1_num_cfgs()) return DH_EINVAL;
   if (a.x_u8 && cfg >= kNumCfgs) return DH_EUNSUPPORTED;
+  if (a.w_split >= 5) {                  // the extended split-bf16 scope (5 / 6 / 7): its own rule, refused layers run on no other kernel
+    if (cfg >= gemm1x1_split_num_cfgs()) return DH_EINVAL;
+    return launch_gemm1x1_split_wide(a, cfg, epi, s);
+  }
   if (a.w_split) {                       // split-bf16 weights (1 / 3 / 4: three / two / one part): only the LDS-DMA GEMM family reads that packing
     if (a.x_u8 || !gemm1x1_eligible(a)) return DH_EUNSUPPORTED;
     if (cfg >= gemm1x1_split_num_cfgs()) return DH_EINVAL;

@@ -24,7 +24,7 @@ namespace {
 template <int P, int WM, int WN, int TN, bool RELU, bool PRE>
 __global__ __launch_bounds__(WM* WN * 64, 2) void convt2x2s_kernel(const ConvArgs p, const int epi_vec, const int cb) {
   constexpr int TM = 1, NS = 2;
-  constexpr bool UP2 = false, KXK = false, D2S = true;
+  constexpr bool UP2 = false, KXK = false, D2S = true, K16 = false;
 #include "gemm1x1s_body.h"
 }
 

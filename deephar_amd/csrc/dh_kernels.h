@@ -32,6 +32,8 @@ bool conv_stem_eligible(const ConvArgs& a);
 int gemm1x1_split_num_cfgs();
 bool gemm1x1_split_eligible(const ConvArgs& a);
 int conv_split_parts(int w_split);   // bf16 parts per operand of a split packing (w_split 1 / 3 / 4 -> 3 / 2 / 1), else 0
+bool gemm1x1_split_wide_eligible(const ConvArgs& a);   // the extended scope, w_split 5 / 6 / 7 (gemm1x1s_ext.hip)
+int conv_split_wide_base(int w_split);                 // 5 / 6 / 7 -> 1 / 3 / 4 (the same packing and arithmetic), else 0
 bool conv_halo_eligible(const ConvArgs& a);
 int conv_halo_num_cfgs();
 int launch_dwconv(const DwArgs& a, hipStream_t s);

@@ -155,7 +155,7 @@ __device__ __forceinline__ void mfma_products(const Frag<P> (&a)[TM], const bf16
 // The body is shared, as text, with the transposed convolution of convt2x2s.hip (gemm1x1s_body.h says why).
 template <int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, int NS = 2, int P = 3>
 __global__ __launch_bounds__(WM* WN * 64, WM * WN >= 8 ? 2 : 2) void gemm1x1s_kernel(const ConvArgs p, const int epi_vec) {
-  constexpr bool PRE = false, D2S = false;
+  constexpr bool PRE = false, D2S = false, K16 = false;
   constexpr int cb = 0;
 #include "gemm1x1s_body.h"
 }

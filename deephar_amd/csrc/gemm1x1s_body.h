@@ -1,5 +1,5 @@
 // The body of the split-bf16 LDS-DMA GEMM kernels, as TEXT: included inside a __global__ function that provides
-//   template / constexpr values  WM, WN, TM, TN, UP2, RELU, KXK, NS, P, PRE, D2S
+//   template / constexpr values  WM, WN, TM, TN, UP2, RELU, KXK, NS, P, PRE, D2S, K16
 //   variables                    p (const ConvArgs, the KERNEL ARGUMENT itself), epi_vec, cb (D2S: columns per output-pixel block)
 // gemm1x1s.hip (gemm1x1s_kernel: the convolution, PRE = D2S = false) and convt2x2s.hip (convt2x2s_kernel: the transposed 2x2 /
 // stride-2 convolution -- the same main loop in front of the depth-to-space epilogue, D2S, with that layer's BatchNormalization
@@ -7,9 +7,12 @@
 // Text rather than a device function on purpose: behind a function boundary (const ConvArgs& or by value, always inlined) hipcc
 // no longer treats the fields of the kernel argument as wave-uniform everywhere -- the epilogues' scalar buffer offsets then
 // go through readfirstlane loops (74-114 more instructions per kernel, measured on the instantiations of gemm1x1s_p1.hip).
+// K16 (gemm1x1s_ext.hip: K x K with Cin % 16 == 0): the tap-major loop resolves (kh, kw, c0) per 16-channel HALF of the K-step
+// instead of once per step, so a step may hold two taps; LDS layout, fragment reads, split and MFMA stream are those of KXK.
 // Helpers (dma16, lds_rd, split8, mfma_products, ...) are those of gemm1x1s.hip, which must be included first.
   static_assert(!(PRE && (KXK || UP2 || TM != 1)), "the BN prologue is built for the pipelined pointwise loop");
   static_assert(!(D2S && (KXK || UP2)), "the depth-to-space epilogue follows the plain pointwise main loop");
+  static_assert(!K16 || KXK, "per-half taps are a form of the tap-major K x K loop");
   constexpr int NT = WM * WN * 64;
   constexpr bool PIPELINED = TM == 1;                    // software-pipelined K loop (below); else one chunk at a time
   constexpr int BM = WM * TM * 32;
@@ -62,7 +65,8 @@
       a_off[ps] = ((unsigned)m * p.ldx + a_slot[ps]) * 4u;
     }
   }
-  const int chunks_per_tap = KXK ? p.Cin / BK : 1;
+  const int chunks_per_tap = KXK ? p.Cin / (K16 ? 16 : BK) : 1;
+  const bool a_hi = a_slot[0] >= 16;                      // K16: the lane's slot lies in the second 16-k half (the same in every pass)
   // packed split weight: 16-byte unit (kg, part, n) at ((kg * P + part) * Np + n) * 16 bytes
   unsigned b_off[BPASS];
 #pragma unroll
@@ -78,7 +82,17 @@
     float* sA = smem + stage * STAGE;
     float* sB = sA + BM * BK;
     int kh = 0, kw = 0, c0 = 0;
-    if constexpr (KXK) {
+    int kh1 = 0, kw1 = 0, c1 = 0;                           // K16: the second half's tap (wave-uniform like the first's)
+    if constexpr (K16) {                                  // half k16 = 2 kt + h: tap k16 / (Cin / 16), c0 = (k16 mod (Cin / 16)) * 16
+      const int tap = (2 * kt) / chunks_per_tap;
+      c0 = (2 * kt - tap * chunks_per_tap) * 16;
+      kh = tap / p.KW;
+      kw = tap - kh * p.KW;
+      const int tap1 = (2 * kt + 1) / chunks_per_tap;
+      c1 = (2 * kt + 1 - tap1 * chunks_per_tap) * 16;
+      kh1 = tap1 / p.KW;
+      kw1 = tap1 - kh1 * p.KW;
+    } else if constexpr (KXK) {
       const int tap = kt / chunks_per_tap;
       c0 = (kt - tap * chunks_per_tap) * BK;
       kh = tap / p.KW;
@@ -86,7 +100,13 @@
     }
 #pragma unroll
     for (int ps = 0; ps < APASS; ++ps) {
-      if constexpr (KXK) {                                // padding taps: out-of-range offset -> zeros
+      if constexpr (K16) {                                // padding taps and halves beyond K: out-of-range offset -> zeros
+        const int ih = a_ih0[ps] + (a_hi ? kh1 : kh), iw = a_iw0[ps] + (a_hi ? kw1 : kw);
+        const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W && (2 * kt + (a_hi ? 1 : 0)) * 16 < p.K;
+        const unsigned off =
+            ok ? ((unsigned)(a_pix[ps] + ih * p.W + iw) * p.ldx + (a_hi ? c1 : c0) + (a_slot[ps] & 15)) * 4u : OOB;
+        dma16(rs_x, sA + (ps * NT + wave_u * 64) * 4, off, 0);
+      } else if constexpr (KXK) {                         // padding taps: out-of-range offset -> zeros
         const int ih = a_ih0[ps] + kh, iw = a_iw0[ps] + kw;
         const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W && kt * BK < p.K;
         const unsigned off = ok ? ((unsigned)(a_pix[ps] + ih * p.W + iw) * p.ldx + c0 + a_slot[ps]) * 4u : OOB;

@@ -15,6 +15,7 @@ from .. import _lib
 from . import packing
 
 SPLIT_CODES = {'bf16x3': 1, 'bf16x2': 3, 'bf16': 4}      # Plan.gemm_precision -> dh_conv_args.w_split (packing.SPLIT_PARTS)
+WIDE_SPLIT_CODES = {'bf16x3': 5, 'bf16x2': 6, 'bf16': 7}  # the same under Plan.gemm_scope == 'extended' (packing.WIDE_SPLIT_PARTS)
 
 BN_EPS = 1e-3  # keras BatchNormalization default epsilon
 
@@ -48,7 +49,8 @@ class WeightStore:
     def conv_weight(self, p, split=0):
         """split = dh_conv_args.w_split: 0 fp32 tap-major, 1 / 3 / 4 the split-bf16 packing with three / two / one part,
         2 fp32 chunk-major (halo-resident K x K kernel); different packings of one Param are kept side by side when
-        several are in use."""
+        several are in use.  5 / 6 / 7 (the extended scope) are the bytes of 1 / 3 / 4 and share their tensor."""
+        split = packing.WIDE_SPLIT_BASE.get(int(split), int(split))
         key = (id(p), int(split))
         ent = self.conv.get(key)
         if ent is None or ent[3] != p.version:
@@ -227,10 +229,18 @@ class BoundPlan:
         """dh_conv_args.w_split of a conv step: 1 / 3 / 4 = split-bf16 (plan.gemm_precision == 'bf16x3' / 'bf16x2' / 'bf16'
         and the library takes the layer: dh_conv2d_split_eligible, one rule for the three), 2 = fp32 chunk-major for the halo-resident K x K kernel
         (dh_conv2d_halo_eligible: a rule on the per-frame geometry), else 0.  The LIBRARY decides, asked with the launch's
-        own argument struct before the weights are packed -- a layer is never bound with a packing its launch rejects."""
-        code = SPLIT_CODES.get(getattr(self.plan, 'gemm_precision', 'f32'))
-        if code and self.lib.dh_conv2d_split_eligible(C.byref(args)):
-            return code
+        own argument struct before the weights are packed -- a layer is never bound with a packing its launch rejects.
+        Under plan.gemm_scope == 'extended' the wider rule is asked instead (dh_conv2d_split_wide_eligible) and the layer is
+        bound with the extended scope's code, 5 / 6 / 7; a layer it refuses falls to halo / fp32 as under 'standard'."""
+        mode = getattr(self.plan, 'gemm_precision', 'f32')
+        if getattr(self.plan, 'gemm_scope', 'standard') == 'extended':
+            code = WIDE_SPLIT_CODES.get(mode)
+            if code and self.lib.dh_conv2d_split_wide_eligible(C.byref(args)):
+                return code
+        else:
+            code = SPLIT_CODES.get(mode)
+            if code and self.lib.dh_conv2d_split_eligible(C.byref(args)):
+                return code
         if self.plan.rules.halo_conv and self.lib.dh_conv2d_halo_eligible(C.byref(args)):
             return 2
         return 0
@@ -745,7 +755,7 @@ class BoundPlan:
             ncfg = ncfgs[step.kind]
             cargs = args[0]._obj
             sig = (self.n, step.kind) + self._conv_signature(step) + ((('u8',) if cargs.x_u8 else ())) + \
-                ((({1: 'bf16x3', 2: 'halo', 3: 'bf16x2', 4: 'bf16'}[cargs.w_split],) if cargs.w_split else ()))
+                ((({1: 'bf16x3', 2: 'halo', 3: 'bf16x2', 4: 'bf16', 5: 'bf16x3', 6: 'bf16x2', 7: 'bf16'}[cargs.w_split],) if cargs.w_split else ()))
             if cargs.w_split:
                 ncfg = lib.dh_conv2d_num_halo_tile_cfgs() if cargs.w_split == 2 else lib.dh_conv2d_num_split_tile_cfgs()
             if step.kind == 'conv' and lib.dh_conv2d_uses_split_k(args[0]):

@@ -68,6 +68,8 @@ def unpack_conv(packed, kh, kw, cin, cout):
 
 
 SPLIT_PARTS = {1: 3, 3: 2, 4: 1}      # dh_conv_args.w_split of a split packing -> bf16 parts per operand
+WIDE_SPLIT_PARTS = {5: 3, 6: 2, 7: 1}  # the same for the extended scope's codes: the packings of 1 / 3 / 4 byte for byte
+WIDE_SPLIT_BASE = {5: 1, 6: 3, 7: 4}   # extended-scope code -> the standard code with the same packing
 
 
 def pack_conv_split(w_hwio, parts=3):

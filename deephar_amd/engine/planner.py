@@ -209,6 +209,7 @@ class Plan:
         self.params = []       # ordered unique graph.Param list
         self.nstreams = 1
         self.gemm_precision = 'f32'   # 'bf16x3' / 'bf16x2' / 'bf16': eligible convs run split-bf16 on the bf16 matrix cores (executor)
+        self.gemm_scope = 'standard'  # 'extended': a split mode also takes BN-prologue pointwise and Cin % 16 K x K convs (executor)
         self.rules = RuleSet()        # the rule switches the plan was built under (build_plan: read once, recorded here)
 
     @property
@@ -1539,15 +1540,19 @@ class Planner:
 
 
 GEMM_PRECISIONS = ('f32', 'bf16x3', 'bf16x2', 'bf16')    # Plan.gemm_precision: the executor maps it to dh_conv_args.w_split
+GEMM_SCOPES = ('standard', 'extended')                   # Plan.gemm_scope: which layers a split mode reaches (no effect under 'f32')
 
 
-def build_plan(inputs, outputs, nstreams=1, gemm_precision='f32', stream_policy='list', rules=None):
+def build_plan(inputs, outputs, nstreams=1, gemm_precision='f32', stream_policy='list', rules=None, gemm_scope='standard'):
     """rules: the RuleSet the plan is built and later bound under; None = RuleSet.from_env(), read here, once."""
     rules = RuleSet.from_env() if rules is None else rules
     if gemm_precision not in GEMM_PRECISIONS:
         raise ValueError("gemm_precision must be one of %s, got %r" % ('/'.join(map(repr, GEMM_PRECISIONS)), gemm_precision))
     if stream_policy not in ('list', 'tail'):
         raise ValueError("stream_policy must be 'list' or 'tail', got %r" % (stream_policy,))
+    if gemm_scope not in GEMM_SCOPES:
+        raise ValueError("gemm_scope must be one of %s, got %r" % ('/'.join(map(repr, GEMM_SCOPES)), gemm_scope))
     plan = Planner(inputs, outputs, nstreams, stream_policy, rules).run()
     plan.gemm_precision = gemm_precision
+    plan.gemm_scope = gemm_scope
     return plan

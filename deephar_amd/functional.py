@@ -46,12 +46,13 @@ def pack_conv_weight(w_hwio, device='cuda'):
 def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=None, pre_relu=False,
            post_scale=None, post_shift=None, post_relu=False, res1=None, res2=None, up2=False, tile_cfg=-1,
            packed=None, in_lut=None, split=False, halo=False, res2_down=False, pool2=False, x_resample=0, seg=None,
-           precision=None):
+           precision=None, scope='standard'):
     """Fused conv (see dh_conv2d_f32).  x [N,H,W,Cin]; w_hwio numpy [kh,kw,Cin,Cout].  A uint8 `x` needs
     `in_lut` (float32 [Cin,256] device tensor, engine.executor.normalization_lut): bytes are normalised on load.
     precision: None / 'f32' (fp32 matrix path), or 'bf16x3' / 'bf16x2' / 'bf16' -- the split-bf16 GEMM with three / two / one
     bf16 part per operand (dh_conv_args.w_split = 1 / 3 / 4); split=True means 'bf16x3'.  A `packed` weight must have been
-    packed for the same mode."""
+    packed for the same mode.  scope='extended': the mode's extended-scope code (w_split = 5 / 6 / 7, the same packing), which
+    also takes a pointwise convolution with a BN prologue and K x K with Cin % 16 == 0 (dh_conv2d_split_wide_eligible)."""
     torch = _t()
     if x.dtype == torch.uint8:
         if in_lut is None or tuple(in_lut.shape) != (x.shape[-1], 256):
@@ -96,6 +97,10 @@ def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=
     up = 2 if up2 else 1
     y = torch.empty((n, oh * up, ow * up, cout), dtype=torch.float32, device=x.device)
     a = _lib.ConvArgs()
+    if scope not in ('standard', 'extended'):
+        raise ValueError("scope must be 'standard' or 'extended', got %r" % (scope,))
+    if scope == 'extended' and w_split:
+        w_split = {1: 5, 3: 6, 4: 7}[w_split]
     a.w_split = 2 if halo else w_split
     a.x, a.w, a.y = _p(x), _p(wt), _p(y)
     a.pre_scale, a.pre_shift, a.post_scale, a.post_shift = _p(pre_scale), _p(pre_shift), _p(post_scale), _p(post_shift)

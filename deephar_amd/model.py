@@ -22,7 +22,8 @@ class CallRec:
         self.model, self.inputs, self.outputs = model, list(inputs), list(outputs)
 
 
-_ENGINE_CHOICES = {'stream_policy': ('list', 'tail'), 'gemm_precision': ('f32', 'bf16x3', 'bf16x2', 'bf16')}
+_ENGINE_CHOICES = {'stream_policy': ('list', 'tail'), 'gemm_precision': ('f32', 'bf16x3', 'bf16x2', 'bf16'),
+                   'gemm_scope': ('standard', 'extended')}
 
 
 class Model:
@@ -58,6 +59,10 @@ class Model:
         # product) or one part and one product (~2^-8, plain bf16 operands); the same layers, the same fp32 accumulation and
         # epilogue, NOT the 1e-3 px class (README "GEMM precision ladder", tests/test_gpu_bf16_modes.py)
         self.gemm_precision = __import__('os').environ.get('DEEPHAR_GEMM', 'f32')
+        # which layers a split mode reaches.  'standard' (default): pointwise and K x K with Cin % 32 == 0, no BN prologue.
+        # 'extended': also the BN-prologue pointwise convolutions and K x K with Cin % 16 == 0 (csrc/gemm1x1s_ext.hip;
+        # about a third of SPNet's conv FLOPs) -- other bits than 'standard' on those layers, none under 'f32'
+        self.gemm_scope = __import__('os').environ.get('DEEPHAR_GEMM_SCOPE', 'standard')
         # the engine's rule switches (engine/rules.py: RuleSet) the plan is built and bound under; None: read from the
         # environment when the plan is built (RuleSet.from_env).  The plan records them either way: self.plan.rules
         self.rules = None
@@ -85,6 +90,7 @@ class Model:
         return property(get, set_)
 
     gemm_precision = _engine_option('gemm_precision')
+    gemm_scope = _engine_option('gemm_scope')
     num_streams = _engine_option('num_streams')
     stream_policy = _engine_option('stream_policy')
     rules = _engine_option('rules')
@@ -219,7 +225,8 @@ class Model:
         if self._plan is None:
             from .engine.planner import build_plan
             self._plan = build_plan(self.inputs, self.outputs, nstreams=self.num_streams,
-                                    gemm_precision=self.gemm_precision, stream_policy=self.stream_policy, rules=self.rules)
+                                    gemm_precision=self.gemm_precision, stream_policy=self.stream_policy, rules=self.rules,
+                                    gemm_scope=self.gemm_scope)
         return self._plan
 
     @property

@@ -211,6 +211,7 @@ class ShardedClipModel:
             if stage is not None:
                 stage.num_streams, stage.gemm_precision = model.num_streams, model.gemm_precision
                 stage.stream_policy, stage.rules = model.stream_policy, model.rules
+                stage.gemm_scope = model.gemm_scope
         if self.head_model is not None:
             self.head_model._stream_role = 'head'                  # (its executor is created on first use: engine/executor.py shared_stream)
         self.frame_fn = frame_fn or self._frame_hip

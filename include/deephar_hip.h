@@ -83,7 +83,13 @@ typedef struct dh_conv_args {
                       (x1 = bf16(x), x2 = bf16(x - x1)), activations after the optional ReLU prologue; with P parts every output is
                       sum_k sum_{i + j <= P + 1} a_i[k] b_j[k] -- three products (a2 b1, a1 b2, a1 b1; ~2^-16 per product) or one
                       (a1 b1; ~2^-8) instead of six, each exact, fp32 accumulation, smallest first, K ascending in every tiling; the
-                      fp32 epilogue is unchanged.  Same shapes, same refusals as 1; any other value is DH_EINVAL */
+                      fp32 epilogue is unchanged.  Same shapes, same refusals as 1.
+                      5 / 6 / 7: the EXTENDED SCOPE of 1 / 3 / 4 (gemm1x1s_ext.hip) -- the same packings byte for byte, the same
+                      arithmetic contract, and for a layer that 1 / 3 / 4 accept the same bits; accepted in addition (see
+                      dh_conv2d_split_wide_eligible): a pointwise convolution with a BatchNormalization prologue (operand =
+                      relu?(fmaf(x, pre_scale, pre_shift)), the one fused multiply-add of the fp32 kernel, then split) and a dense
+                      K x K convolution with Cin % 16 == 0.  A layer that rule refuses returns DH_EUNSUPPORTED and is never
+                      run on another kernel.  Any other value is DH_EINVAL */
   int32_t res2_down; /* 1: res2 is at HALF the output resolution, [N, OH/2, OW/2, Cout]: out(oh, ow) += res2(oh/2, ow/2), i.e.
                         add([., UpSampling2D((2, 2))(res2)]) with the up-sampling folded into the residual read
                         (reception.py:122-127: `b = UpSampling2D((2, 2))(b); x = add([a, b])` fused into the convolution
@@ -153,6 +159,14 @@ int dh_conv2d_uses_first_layer_kernel(const dh_conv_args* a);
  * float input, no BN prologue, not a split-K layer, operands within the 32-bit buffer offsets of the kernel.  A
  * binding asks this BEFORE it packs the weights, so that a layer is never bound with a packing its launch rejects. */
 int dh_conv2d_split_eligible(const dh_conv_args* a);
+/* 1 when dh_conv2d_f32 would accept this convolution with w_split = 5, 6 or 7, the extended scope of the same three modes --
+ * again one rule for the three, on the layer's per-frame geometry and alignment only (never on timing or on `w` / `w_split`;
+ * the batch size only enters through the 32-bit buffer offsets, as above): everything dh_conv2d_split_eligible accepts, and
+ * (a) a pointwise convolution with a BatchNormalization prologue (pre_scale AND pre_shift, Kp <= 4096: the tables live in
+ * LDS), (b) a dense K x K convolution with Cin % 16 == 0 at any stride and explicit padding; both with a 16-byte aligned
+ * float input, no fused up-sampling, not a split-K layer, not the first layer.  K x K with Cin % 16 != 0 or with a BN
+ * prologue stays refused.  A binding asks this BEFORE it packs the weights. */
+int dh_conv2d_split_wide_eligible(const dh_conv_args* a);
 /* 1 when this convolution belongs to the halo-resident K x K kernel (conv_halo.hip): dense K x K, stride 1, Cin % 16
  * == 0 but Cin % 32 != 0 (the layers the LDS-DMA tap-major kernel cannot take), maps of >= 1024 pixels per frame whose
  * rows tile into runs of 128 output pixels, 16-byte aligned float input, no BN prologue / fused up-sampling.  (The
