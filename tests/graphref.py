@@ -7,6 +7,12 @@ oracle/ops.py -- nothing is fused, re-associated or viewed -- so whatever the pl
 it: float64 is the arbiter, float32 is "what plain fp32 does".  tests/test_graphref_host.py pins the interpreter to the
 hand-written oracles.
 
+The split-bf16 ladder inside the interpreter: evaluate(..., split=(parts, param_ids)) evaluates every dense convolution (a
+`conv` node, the pointwise half of a `sepconv` node) and every `convtranspose` node whose weight Param is in `param_ids` as
+E_parts of tests/bf16_modes_ref.py -- the operand it receives rounded to float32, both operands split into bf16 parts, exact
+products.  `split_param_ids` reads the ids off a bound model: the fp64 interpreter then IS the mode the plan was bound with,
+layer by layer (tests/test_synth_split_host.py, tests/test_gpu_synth_graphs_split.py).  Without the hook nothing changes.
+
 What the IR does not record is derived: the bottom / right padding of a convolution or pooling from its output shape
 (max((OH - 1) * sh + kh - H - pt, 0)); leading clip dims are folded into the batch.
 """
@@ -17,6 +23,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import bf16_modes_ref as B
 import paritylog
 import resample_ref as R
 from deephar_amd import graph as G
@@ -25,6 +32,7 @@ from oracle import ops
 SKIPPABLE = ('bn', 'relu', 'scale', 'sigmoid', 'add')      # shape-preserving nodes `skip=` can turn into the identity
 DECODER_OPS = ('expect2d', 'jointprob')      # the read-outs compare_decoder has a conditioned tolerance for
 LAYER_COST = dict(conv=1, sepconv=2, convtranspose=1)
+SPLIT_CODES = (1, 3, 4, 5, 6, 7)             # dh_conv_args.w_split of the split-bf16 packings (0: fp32, 2: the halo kernel's)
 
 
 def _param(layer, role, dtype):
@@ -32,6 +40,32 @@ def _param(layer, role, dtype):
         if p.role == role:
             return torch.from_numpy(p.value).to(dtype)
     return None
+
+
+def _parts(layer, role, split):
+    """the number of bf16 parts the layer's `role` kernel is evaluated with under the hook `split`, 0 for plain arithmetic"""
+    if split is None:
+        return 0
+    parts, ids = split
+    return parts if any(p.role == role and id(p) in ids for p in layer.params) else 0
+
+
+def _conv2d(x, kernel, strides, parts):
+    if parts:
+        return B.conv_ep(ops.conv2d, x, kernel, strides, 'valid', parts)
+    return ops.conv2d(x, kernel, strides, 'valid')
+
+
+def split_param_ids(m):
+    """The weight Params of the convolution / transposed-convolution steps a BOUND model runs with a split-bf16 packing
+    (attrs['w_split'] in SPLIT_CODES), as a set of id()s for evaluate(split=(parts, ids)); the parts of a merged
+    convolution's ConcatParam each.  Call it after the first bind (a predict): the executor writes w_split when it binds."""
+    ids = set()
+    for s in m.plan.steps:
+        if s.kind in ('conv', 'convtranspose') and s.attrs.get('w_split', 0) in SPLIT_CODES:
+            w = s.params['w']
+            ids.update(id(p) for p in getattr(w, 'parts', [w]))
+    return ids
 
 
 def _fold(x, nd):
@@ -52,20 +86,23 @@ def _pad(x, a, out_shape, value=0.0):
     return x
 
 
-def _eval_node(node, xs, dtype):
+def _eval_node(node, xs, dtype, split=None):
     op, a = node.op, node.attrs
     shape = node.outputs[0].shape
     strides = (a.get('sh', 1), a.get('sw', 1))
     if op == 'conv':
         x = _pad(_fold(xs[0], 3), a, shape)
-        return ops.conv2d(x, _param(node.layers['conv'], 'conv', dtype), strides, 'valid')
+        return _conv2d(x, _param(node.layers['conv'], 'conv', dtype), strides, _parts(node.layers['conv'], 'conv', split))
     if op == 'sepconv':
         layer = node.layers['sepconv']
         x = _pad(_fold(xs[0], 3), a, shape)
         x = ops.depthwise_conv2d(x, _param(layer, 'depthwise', dtype), strides, 'valid')
-        return ops.conv2d(x, _param(layer, 'conv', dtype), (1, 1), 'valid')
+        return _conv2d(x, _param(layer, 'conv', dtype), (1, 1), _parts(layer, 'conv', split))
     if op == 'convtranspose':
-        return R.conv_transpose2x2(_fold(xs[0], 3), _param(node.layers['convt'], 'convt', dtype))
+        x, k, parts = _fold(xs[0], 3), _param(node.layers['convt'], 'convt', dtype), _parts(node.layers['convt'], 'convt', split)
+        if parts:        # (tests/test_gpu_convt_split.py: _convt)
+            return B.conv_ep(lambda a_, k_, _s, _p: R.conv_transpose2x2(a_, k_), x, k, None, None, parts)
+        return R.conv_transpose2x2(x, k)
     if op == 'bn':
         layer = node.layers['bn']
         return ops.batchnorm(xs[0], _param(layer, 'beta', dtype), _param(layer, 'mean', dtype), _param(layer, 'var', dtype),
@@ -131,10 +168,12 @@ def _eval_node(node, xs, dtype):
     raise NotImplementedError('graphref: no statement for op %r' % op)
 
 
-def evaluate(inputs, outputs, feeds, dtype, taps=None, skip=None):
+def evaluate(inputs, outputs, feeds, dtype, taps=None, skip=None, split=None):
     """Evaluate the graph inputs -> outputs on the arrays `feeds` ([N, ...] each) at `dtype`; one numpy array per output.
     taps (a dict) receives every tensor, the inputs included, by uid.  skip=<node>: that shape-preserving node (SKIPPABLE;
-    an add is reduced to its first operand) is the identity -- the mutation the host test uses to show that the bar bites."""
+    an add is reduced to its first operand) is the identity -- the mutation the host test uses to show that the bar bites.
+    split=(parts, param_ids): the layers whose weight Param is in param_ids (split_param_ids) are evaluated as E_parts, the
+    split-bf16 mode with `parts` bf16 parts per operand; every other layer, and everything without the hook, as before."""
     if skip is not None and skip.op not in SKIPPABLE:
         raise ValueError('only %s nodes can be skipped, not %r' % ('/'.join(SKIPPABLE), skip.op))
     n = int(np.asarray(feeds[0]).shape[0])
@@ -144,7 +183,7 @@ def evaluate(inputs, outputs, feeds, dtype, taps=None, skip=None):
             val[t.uid] = torch.from_numpy(np.ascontiguousarray(x)).to(dtype).reshape((n,) + t.shape)
         for node in G.topo_nodes(outputs):
             xs = [val[t.uid] for t in node.inputs]
-            y = xs[0] if node is skip else _eval_node(node, xs, dtype)
+            y = xs[0] if node is skip else _eval_node(node, xs, dtype, split)
             val[node.outputs[0].uid] = y.reshape((n,) + node.outputs[0].shape)
     if taps is not None:
         taps.update({uid: v.numpy() for uid, v in val.items()})

@@ -1,11 +1,17 @@
 """Synthetic graphs out of the public `layers` vocabulary, one per planner guard and each with its near-miss twin, plus a
-seeded generator of random feature-map DAGs.  TEST INFRASTRUCTURE (tests/test_graphref_host.py, tests/test_gpu_synth_graphs.py).
+seeded generator of random feature-map DAGs.  TEST INFRASTRUCTURE (tests/test_graphref_host.py, tests/test_gpu_synth_graphs.py;
+tests/test_synth_split_host.py and tests/test_gpu_synth_graphs_split.py for the split-bf16 ladder).
 
 Every graph is a function (H, W, C) -> (inputs, outputs).  `ZOO` lists them with the shapes they are built at, the plan
 feature they exist for (`FEATURES`) and whether the default plan must show it there: a graph in which the guard holds says
 True, its twin -- one clause of the guard broken -- says False.  Shapes: 16 x 16 maps (256 pixels: the split-K "skinny"
 kernel once K >= 64) and 32 x 32 maps (the general / LDS-DMA / halo families), each with an aligned channel count (48) and an
 odd one (34: scalar paths, channel offsets that are no multiples of four); graphs tied to one geometry say so.
+
+The split-bf16 ladder (Model.gemm_precision) is tested on the same graphs at `SPLIT_SHAPES` (`split_graphs`): 32 x 32 x 48
+(pointwise layers of the standard class, 3 x 3 layers with Cin % 32 == 16 of the extended class), 32 x 32 x 64 (K x K layers of
+the standard class) and 16 x 16 x 48 (K = 48 < 64: pointwise layers stay off the skinny kernel), and at 32 x 32 x 34, where
+next to nothing is eligible.
 """
 import dataclasses
 
@@ -17,6 +23,8 @@ from deephar_amd.engine.rules import RuleSet
 SIZES = ((16, 16), (32, 32))
 CHANNELS = (48, 34)
 STD = tuple((h, w, c) for (h, w) in SIZES for c in CHANNELS)
+SPLIT_SHAPES = ((32, 32, 48), (32, 32, 64), (16, 16, 48))      # the shapes of the split-bf16 leg
+UNALIGNED_SHAPE = (32, 32, 34)                                  # ... and the one where the views are unaligned
 
 BOOL_RULES = tuple(f.name for f in dataclasses.fields(RuleSet) if f.type is bool)
 
@@ -166,6 +174,25 @@ def pose_times_conf(H, W, C, tap=False):
 def pose_times_conf_tapped(H, W, C):
     """... the coordinates are a model output as well: they have to be written"""
     return pose_times_conf(H, W, C, tap=True)
+
+
+# ---- channel-slice readers (the input operand of a GEMM as a view) ----------------------------------------------------------
+def _slice_reader(H, W, C, start):
+    x = L.Input((H, W, C))
+    wide = L.conv(x, C + 24, (1, 1), name='wide')
+    return [x], [wide, L.conv(wide.channels(start, start + C), C, (1, 1), name='p'),
+                 L.conv(wide.channels(start + 4, start + 4 + C), 40, (3, 3), name='k')]
+
+
+def slice_reader(H, W, C):
+    """a 1x1 and a 3x3 convolution each read C channels out of a tensor of C + 24 that is a model output as well, from channel
+    4 and 8 on: x.coff % 4 == 0, x.ld > Cin -- 16-byte aligned views, which the LDS-DMA main loops of the split-bf16 kernels take"""
+    return _slice_reader(H, W, C, 4)
+
+
+def slice_reader_odd(H, W, C):
+    """... from channel 2 and 6 on: the views are 8 bytes off, every GEMM family that loads 16 bytes at a time must refuse them"""
+    return _slice_reader(H, W, C, 2)
 
 
 # ---- R7: pooled second output ----------------------------------------------------------------------------------------
@@ -352,6 +379,8 @@ FEATURES = {
     'xy_times_conf': lambda p: any(s.attrs.get('xy_times_conf') for s in _steps(p, 'sam')),
     'two_bn_prologues': lambda p: sum(1 for s in p.steps if 'pre_bn' in s.params) == 2 and not any(s.name == 'materialize' for s in p.steps),
     'three_eltwise': lambda p: len(_steps(p, 'eltwise')) == 3,
+    # a convolution reads its input through a channel-slab view
+    'x_view': lambda p: any(s.ins['x'].coff != 0 or s.ins['x'].ld != s.ins['x'].C for s in _steps(p, 'conv')),
 }
 
 
@@ -437,6 +466,11 @@ ZOO = (
     Case(learned_resample, 'two_bn_prologues', False),
     Case(learned_resample_bn_twice, 'two_bn_prologues', True),
     Case(eltwise_tail, 'three_eltwise', True),
+    # (the twin's plan is the same: what differs is the library's answer about the misaligned views, tests/test_synth_split_host.py)
+    Case(slice_reader, 'no_copy', True),
+    Case(slice_reader, 'x_view', True),
+    Case(slice_reader_odd, 'no_copy', True),
+    Case(slice_reader_odd, 'x_view', True),
 )
 
 
@@ -449,6 +483,20 @@ def graphs():
                 seen.add((c.name,) + s)
                 out.append((c.fn,) + s)
     return out
+
+
+def split_graphs(shapes=SPLIT_SHAPES):
+    """every (graph function, H, W, C) of the split-bf16 leg: each zoo graph at each of `shapes`.  Every zoo graph can be
+    built at any even H, W >= 16 and any C (conv_pool and pools_cat* at their 32-column form: 32 x 32, C = 48 and 64; the
+    action heads' (T, J) plane of pools_cat* and kxk_siblings stays with the fp32 leg)."""
+    fns = []
+    for c in ZOO:
+        if c.fn not in fns:
+            fns.append(c.fn)
+    return [(fn,) + tuple(s) for fn in fns for s in shapes]
+
+
+SPLIT_RANDOM_SHAPES = ((32, 32, 48), (32, 32, 64))
 
 
 # ---- the generator -----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,9 @@
 """Fused plans of synthetic graphs (tests/synthgraphs.py: one graph per planner guard with its near-miss twin, and seeded random
 DAGs) against the fp64 graph interpreter of tests/graphref.py: under the default rules, with every switch off and with one
-switch off; with the arena poisoned; across engine settings and through the C-level plan executor."""
+switch off; with the arena poisoned; across engine settings and through the C-level plan executor.
+
+This is the fp32 leg (gemm_precision='f32').  tests/test_gpu_synth_graphs_split.py is the split-bf16 leg: the same graphs bound
+under 'bf16x3' / 'bf16x2' / 'bf16' and both scopes, held to the interpreter with the mode inside (graphref.evaluate(split=...))."""
 import ctypes
 import os
 import sys
