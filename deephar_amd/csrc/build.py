@@ -16,12 +16,7 @@ INCLUDE = os.path.join(ROOT, "include")
 SOURCES = ["conv_igemm.hip", "gemm1x1.hip", "convt2x2.hip", "convt2x2s.hip", "gemm1x1s.hip", "gemm1x1s_p2.hip", "gemm1x1s_p1.hip",
            "gemm1x1s_ext.hip", "gemm1x1s_ext_p2.hip", "gemm1x1s_ext_p1.hip", "conv_splitk.hip", "conv_halo.hip", "conv_stem.hip", "spatial.hip", "decoder.hip",
            "capi.hip", "plan.hip"]
-HEADERS = [os.path.join(HERE, "dh_kernels.h"), os.path.join(HERE, "conv_common.h"), os.path.join(HERE, "dw_lds.h"),
-           os.path.join(HERE, "gemm1x1s_body.h"),
-           os.path.join(INCLUDE, "deephar_hip.h")]
-INCLUDES = {"gemm1x1s_p2.hip": ["gemm1x1s.hip"], "gemm1x1s_p1.hip": ["gemm1x1s.hip"], "convt2x2.hip": ["gemm1x1.hip"],
-            "convt2x2s.hip": ["gemm1x1s.hip"], "gemm1x1s_ext.hip": ["gemm1x1s.hip"],
-            "gemm1x1s_ext_p2.hip": ["gemm1x1s.hip", "gemm1x1s_ext.hip"], "gemm1x1s_ext_p1.hip": ["gemm1x1s.hip", "gemm1x1s_ext.hip"]}   # sources that include a source
+HEADERS = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(INCLUDE, "deephar_hip.h")]
 LIB = os.path.join(HERE, "libdeephar_hip.so")
 OBJDIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
@@ -40,7 +35,7 @@ def _stale(target, deps):
 def _compile(src):
     obj = os.path.join(OBJDIR, src.replace(".hip", ".o"))
     path = os.path.join(HERE, src)
-    deps = [path] + HEADERS + [os.path.join(HERE, inc) for inc in INCLUDES.get(src, [])]
+    deps = [path] + HEADERS
     if _stale(obj, deps):
         cmd = [HIPCC] + FLAGS + ["-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

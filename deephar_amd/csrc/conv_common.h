@@ -59,6 +59,16 @@ inline int epi_with_direct(const ConvArgs& a, int epi, bool half_res_residual = 
   return epi | (direct ? 2 : 0);
 }
 
+// Work-groups of a BM x BN tiling of the GEMM [M = N * OH * OW] x [Cout]: the grid's x dimension, so DH_EINVAL outside (0, 2^31)
+template <int BM, int BN>
+inline int gemm_tile_count(const ConvArgs& a, unsigned* tiles) {
+  const long long M = (long long)a.N * a.OH * a.OW;
+  const long long t = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
+  if (t <= 0 || t > 0x7fffffffLL) return DH_EINVAL;
+  *tiles = (unsigned)t;
+  return DH_OK;
+}
+
 // XCD-aware bijective remap: block b runs on XCD b%8; give each XCD a contiguous run of tiles so the
 // workgroups that share one activation tile (consecutive N-tiles) hit the same L2.
 __device__ __forceinline__ int xcd_tile(int b, int nwg) {

@@ -22,39 +22,15 @@
 // tilings (TN = 1, 2, 3) are bit-identical.  Same epilogue as the other MFMA convs (conv_common.h).
 #include <utility>
 #include "conv_common.h"
+#include "lds_dma.h"
 
 namespace dh {
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-constexpr unsigned OOB = 0xfffffff0u;     // beyond every descriptor used here: the load returns zeros
 constexpr int HCH = 16;                   // channels per resident chunk
 constexpr int HPIX = 80;                  // LDS bytes per halo pixel (64 + 16 pad)
 constexpr int HMAXA = 12;                 // halo DMA instructions per wave (<= 48 KB per chunk)
 constexpr int HMAXB = 8;                  // weight-stage DMA passes (KW * BN <= 512)
-
-template <typename RSRC>
-__device__ __forceinline__ void dma16(RSRC rs, char* dst, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)dst, 16, voff, soff, 0, 0);
-#endif
-}
-template <int OFF>
-__device__ __forceinline__ float4 lds_rd(unsigned addr) {
-  float4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ void lgkm_wait() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ float relu1(float v) {      // one integer max (gemm1x1.hip)
-  const int b = __float_as_int(v);
-  return __int_as_float(b > 0 ? b : 0);
-}
-__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w)); }
 
 template <int... Is, typename F>
 __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
@@ -207,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const ConvArgs p, con
       }
     }
     lgkm_wait();
-    // compile-time loop over the 2 KW sub-steps: every fetch and its wait sit in straight-line code (see gemm1x1.hip)
+    // compile-time loop over the 2 KW sub-steps: every fetch and its wait sit in straight-line code (see gemm1x1_body.h)
     static_for<2 * KW>([&](auto U) {
       constexpr int u = decltype(U)::value;
       constexpr int nu = u + 1;
@@ -296,8 +272,6 @@ int launch_kw(const ConvArgs& a, int tn, int epi, const HaloGeom& g, hipStream_t
 
 }  // namespace
 
-bool conv_is_skinny(const ConvArgs& a);
-
 // What the kernel can run: dense K x K with K > 1 somewhere, stride 1 (stride 2 keeps the tap-major kernels: its halo is
 // 4x the output tile), Cin a multiple of 16, float input, 16-byte aligned views, no BN prologue / fused up-sampling,
 // whole-row output tiles of 128 pixels, LDS budget.
@@ -307,8 +281,8 @@ bool conv_halo_supported(const ConvArgs& a0) {
   if (a.x_u8 || a.up2 || a.pre_scale != nullptr || conv_is_skinny(a)) return false;
   if (a.KH * a.KW <= 1 || a.KH > 7 || !(a.KW == 1 || a.KW == 3 || a.KW == 5)) return false;
   if (a.SH != 1 || a.SW != 1 || a.PT < 0 || a.PL < 0) return false;
-  if (a.Cin % HCH || a.Cin < 32 || a.ldx % 4 || (reinterpret_cast<uintptr_t>(a.x) & 15)) return false;
-  if ((long long)a.N * a.H * a.W * a.ldx * 4 > 0xf0000000LL) return false;
+  if (a.Cin % HCH || a.Cin < 32 || a.ldx % 4 || !al16(a.x)) return false;
+  if ((long long)a.N * a.H * a.W * a.ldx * 4 > kMaxBufferBytes) return false;
   if (a.OH * a.OW < 1024) return false;      // small maps keep the tap-major kernels (a per-frame rule: never on N)
   HaloGeom g;
   return geometry(a, 1, &g);
@@ -325,7 +299,7 @@ int conv_halo_num_cfgs() { return 3; }
 
 // cfg: 0, 1, 2 -> TN = 1, 2, 3 (output-channel tile 32, 64, 96); < 0: the widest that fits and divides the work well
 int launch_conv_halo(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  if (!conv_halo_supported(a) || (reinterpret_cast<uintptr_t>(a.w) & 15)) return DH_EUNSUPPORTED;
+  if (!conv_halo_supported(a) || !al16(a.w)) return DH_EUNSUPPORTED;
   if (a.Kp % 32 || a.K != a.KH * a.KW * a.Cin) return DH_EINVAL;
   if (cfg >= 3) return DH_EINVAL;
   int tn = cfg + 1;

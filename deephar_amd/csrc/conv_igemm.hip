@@ -253,9 +253,8 @@ constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 template <int WM, int WN, int TM, int TN>
 int launch_cfg(const ConvArgs& a, bool vec4, int epi, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long tiles = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-  if (tiles <= 0 || tiles > 0x7fffffffLL) return DH_EINVAL;
+  unsigned tiles;
+  if (gemm_tile_count<BM, BN>(a, &tiles) != DH_OK) return DH_EINVAL;
   constexpr int kStage = BM * LDA + BK * BN, kEpi = WM * WN * 32 * (TN * 32 + 4);
   const size_t lds = (size_t)(kStage > kEpi ? kStage : kEpi) * sizeof(float);
   if (a.y_pool != nullptr && !conv_epilogue_pools_for<WM, TM, false>(a)) return DH_EUNSUPPORTED;
@@ -263,11 +262,11 @@ int launch_cfg(const ConvArgs& a, bool vec4, int epi, hipStream_t s) {
     if (!vec4) return DH_EUNSUPPORTED;
     if constexpr (TM * TN >= 6) return DH_EUNSUPPORTED;  // would spill; the dispatcher never asks for it
     else
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, true>), dim3((unsigned)tiles), dim3(NT), lds, s, a, epi);
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, true>), dim3(tiles), dim3(NT), lds, s, a, epi);
   } else if (vec4) {
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false>), dim3((unsigned)tiles), dim3(NT), lds, s, a, epi);
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false>), dim3(tiles), dim3(NT), lds, s, a, epi);
   } else {
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false>), dim3((unsigned)tiles), dim3(NT), lds, s, a, epi);
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false>), dim3(tiles), dim3(NT), lds, s, a, epi);
   }
   return check_launch();
 }
@@ -331,7 +330,6 @@ int launch_conv_igemm(const ConvArgs& a, int cfg, hipStream_t s) {
   // it pairs the k values of an MFMA differently from the tap-major kernels, so its last bits differ from theirs and a
   // layer must never move between the two on a timing-based choice
   if (conv_stem_eligible(a)) return cfg < kNumCfgs + gemm1x1_num_cfgs() ? launch_conv_stem(a, s) : DH_EINVAL;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const int epi = (a.Cout % 4 == 0) && (a.ldy % 4 == 0) && al16(a.y) &&
                   (a.res1 == nullptr || (a.ldr1 % 4 == 0 && al16(a.res1))) &&
                   (a.res2 == nullptr || (a.ldr2 % 4 == 0 && al16(a.res2))) &&

@@ -365,7 +365,6 @@ int skinny_launch_shape(const ConvArgs& a, SkinnyLaunch* o) {
   const long long M = (long long)a.N * a.OH * a.OW;
   o->tiles = ((M + 15) / 16) * ((a.Cout + 15) / 16);
   if (o->tiles <= 0 || o->tiles > 0x3fffffffLL || (long long)a.H * a.W * a.ldx > 0x7fffffffLL || a.Kp % 16 != 0) return DH_EINVAL;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   o->vec = a.Cin % 4 == 0 && a.ldx % 4 == 0 && al16(a.x);
   o->nwv = conv_skinny_waves(a.Kp);
   o->magic_cin = (unsigned)((1ull << 32) / (unsigned)a.Cin + 1ull);
@@ -420,7 +419,6 @@ int launch_conv_splitk_seg(const ConvArgs& a, const ConvSeg& seg, hipStream_t s)
   SkinnyLaunch l;
   if (skinny_launch_shape(a, &l) != DH_OK) return DH_EINVAL;
   if ((long long)a.H * seg.pool_sh * a.W * 2 * a.ldx > 0x7fffffffLL || (long long)a.H * a.W * seg.ldx2 > 0x7fffffffLL) return DH_EINVAL;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   l.vec = l.vec && seg.c_split % 4 == 0 && (seg.x2 == nullptr || (seg.ldx2 % 4 == 0 && al16(seg.x2)));
   switch (l.nwv) {
     case 16: return launch_seg<16>(a, seg, l, s);
@@ -436,7 +434,6 @@ int launch_conv_splitk(const ConvArgs& a, hipStream_t s) {
       a.Kp % 16 != 0)
     return DH_EINVAL;
   if (a.x_resample < 0 || a.x_resample > 3 || (a.x_resample == 1 && ((a.H | a.W) & 1))) return DH_EINVAL;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   // (the vector form is a property of the layer wherever the engine lays tensors out 16-byte aligned; both forms load
   //  the same values and run the same arithmetic: same bits)
   const bool vec = a.Cin % 4 == 0 && a.ldx % 4 == 0 && al16(a.x);

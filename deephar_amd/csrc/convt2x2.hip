@@ -7,9 +7,8 @@
 // depend on neither tiling nor batch size) in front of a depth-to-space epilogue (conv_common.h: d2s_epilogue).
 // Prologue: BatchNormalization (scale / shift) + ReLU on the input, as in the pointwise form.  Epilogue: an optional residual
 // read at the OUTPUT resolution (the pyramid's add([xp, lp[i]]) right behind the unit, spnet.py:303) and an optional ReLU.
-// This translation unit compiles gemm1x1.hip's kernel body a second time, for its own instantiations only.
-#define DH_CONVT_TU
-#include "gemm1x1.hip"
+// The kernel body of gemm1x1.hip (gemm1x1_body.h) is compiled here for this layer's instantiations only.
+#include "gemm1x1_body.h"
 
 namespace dh {
 namespace {
@@ -22,29 +21,21 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void convt2x2_kernel(const ConvArgs
 
 template <int WM, int WN, int TM, int TN, bool RELU, bool PRE>
 int launch_convt_variant(const ConvArgs& a, int vec, int cb, unsigned tiles, hipStream_t s) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  constexpr int kStage = 2 * (BM * BK + BK * BN), kEpi = WM * WN * 32 * (TN * 32 + 4);
-  constexpr size_t kLds = (size_t)(kStage > kEpi ? kStage : kEpi) * sizeof(float);
-  constexpr size_t kMax = kLds + (PRE ? 2 * kMaxPreKp * sizeof(float) : 0);
+  constexpr size_t kMax = gemm_f32_lds(WM, WN, TM, TN, PRE, 0).limit;
   static_assert(kMax <= 160 * 1024, "LDS budget");
-  // PRE: the scale | shift tables sit behind the two stages (the epilogue slab, when larger, only starts after the K loop)
-  const size_t lds = PRE ? std::max(kLds, (size_t)(kStage + 2 * a.Kp) * sizeof(float)) : kLds;
   auto kern = convt2x2_kernel<WM, WN, TM, TN, RELU, PRE>;
   if (kMax > 64 * 1024) {
     static LdsLimit lim;
     lim.raise((const void*)kern, (int)kMax);
   }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(NT), lds, s, a, vec, cb);
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), gemm_f32_lds(WM, WN, TM, TN, PRE, a.Kp).launch, s, a, vec, cb);
   return check_launch();
 }
 
 template <int WM, int WN, int TM, int TN>
 int launch_convt_cfg(const ConvArgs& a, int vec, int cb, hipStream_t s) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long tiles = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-  if (tiles <= 0 || tiles > 0x7fffffffLL) return DH_EINVAL;
-  const unsigned t = (unsigned)tiles;
+  unsigned t;
+  if (gemm_tile_count<WM * TM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
   if (a.pre_scale != nullptr)
     return a.pre_relu ? launch_convt_variant<WM, WN, TM, TN, true, true>(a, vec, cb, t, s)
                       : launch_convt_variant<WM, WN, TM, TN, false, true>(a, vec, cb, t, s);
@@ -65,9 +56,8 @@ int launch_convt2x2(const ConvArgs& a, int cb, int cfg, hipStream_t s) {
     return DH_EINVAL;
   const long long M = (long long)a.N * a.H * a.W;
   if (M > 0x7fffffffLL / 4) return DH_EINVAL;                          // 4 M output pixels are indexed in 32 bits per frame row
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   // the LDS-DMA loads move 16 bytes per lane through 32-bit buffer offsets
-  if (a.Cin % 4 != 0 || a.ldx % 4 != 0 || !al16(a.x) || !al16(a.w) || M * a.ldx * 4 > 0xf0000000LL) return DH_EUNSUPPORTED;
+  if (a.Cin % 4 != 0 || a.ldx % 4 != 0 || !al16(a.x) || !al16(a.w) || M * a.ldx * 4 > kMaxBufferBytes) return DH_EUNSUPPORTED;
   if (a.pre_scale != nullptr && a.Kp > kMaxPreKp) return DH_EUNSUPPORTED;
   const int vec = (cb % 4 == 0) && (a.ldy % 4 == 0) && al16(a.y) && (a.res1 == nullptr || (a.ldr1 % 4 == 0 && al16(a.res1)));
   if (cfg < 0) {

@@ -12,11 +12,9 @@
 // split has the bits of the fp32 kernel's operand.
 // Pointwise only, per-wave tiles of 32 rows (the pipelined loop), two LDS stages: the layer has few rows (M = frames x 16 /
 // 64 / 256 in SPNet) and 1152 ... 1920 columns, so the tilings go down to 32 x 32 to keep 256 CUs busy.
-// This translation unit compiles the kernel body of the family (gemm1x1s_body.h) for its own instantiations only.
-#define DH_CONVT_TU
-#include <algorithm>
-
-#include "gemm1x1s.hip"
+// The kernel body of the family (gemm1x1s_body.h) is compiled here for this layer's instantiations only.
+#include "gemm_family.h"
+#include "split_bf16.h"
 
 namespace dh {
 namespace {
@@ -30,29 +28,21 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void convt2x2s_kernel(const ConvArg
 
 template <int P, int WM, int WN, int TN, bool RELU, bool PRE>
 int launch_convts_variant(const ConvArgs& a, int vec, int cb, unsigned tiles, hipStream_t s) {
-  constexpr int BM = WM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  constexpr int kStage = 2 * (BM * BK + 4 * P * BN * 4), kEpi = WM * WN * 32 * (TN * 32 + 4);
-  constexpr size_t kLds = (size_t)(kStage > kEpi ? kStage : kEpi) * sizeof(float);
-  constexpr size_t kMax = PRE ? std::max(kLds, (size_t)(kStage + 2 * kMaxPreKp) * sizeof(float)) : kLds;
+  constexpr size_t kMax = gemm_split_lds(P, WM, WN, 1, TN, 2, PRE, 0).limit;
   static_assert(kMax <= 160 * 1024, "LDS budget");
-  // PRE: the scale | shift tables sit behind the two stages (the epilogue slab, when larger, only starts after the K loop)
-  const size_t lds = PRE ? std::max(kLds, (size_t)(kStage + 2 * a.Kp) * sizeof(float)) : kLds;
   auto kern = convt2x2s_kernel<P, WM, WN, TN, RELU, PRE>;
   if (kMax > 64 * 1024) {
     static LdsLimit lim;
     lim.raise((const void*)kern, (int)kMax);
   }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(NT), lds, s, a, vec, cb);
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), gemm_split_lds(P, WM, WN, 1, TN, 2, PRE, a.Kp).launch, s, a, vec, cb);
   return check_launch();
 }
 
 template <int P, int WM, int WN, int TN>
 int launch_convts_cfg(const ConvArgs& a, int vec, int cb, hipStream_t s) {
-  constexpr int BM = WM * 32, BN = WN * TN * 32;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long tiles = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-  if (tiles <= 0 || tiles > 0x7fffffffLL) return DH_EINVAL;
-  const unsigned t = (unsigned)tiles;
+  unsigned t;
+  if (gemm_tile_count<WM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
   if (a.pre_scale != nullptr)
     return a.pre_relu ? launch_convts_variant<P, WM, WN, TN, true, true>(a, vec, cb, t, s)
                       : launch_convts_variant<P, WM, WN, TN, false, true>(a, vec, cb, t, s);
@@ -74,36 +64,35 @@ int launch_convts_parts(const ConvArgs& a, int cfg, int vec, int cb, hipStream_t
   return DH_EINVAL;
 }
 
-}  // namespace
-
-int convt2x2_split_num_cfgs() { return kNumCfgs; }
-
-// What launch_convt2x2_split accepts, for every `parts`: a rule on geometry and alignment (the weight pointer is not looked
-// at: a binding asks before it packs; no pointer is dereferenced).  `a` describes the GEMM as for launch_convt2x2.
-bool convt2x2_split_eligible(const ConvArgs& a, int cb) {
-  if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.Cin <= 0 || cb <= 0 || a.Cout != 4 * cb) return false;
-  if (a.Kp % BK != 0 || a.Np % 32 != 0 || a.Kp < a.Cin || a.Np < a.Cout || a.ldx < a.Cin || a.ldy < cb ||
-      (a.res1 != nullptr && a.ldr1 < cb))
-    return false;
-  const long long M = (long long)a.N * a.H * a.W;
-  if (M > 0x7fffffffLL / 4) return false;
-  // the LDS-DMA loads move 16 bytes per lane through 32-bit buffer offsets (activations, packed split weight)
-  if (a.Cin % 4 != 0 || a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x) & 15) != 0) return false;
-  if (M * a.ldx * 4 > 0xf0000000LL || (long long)a.Kp * a.Np * 6 > 0xf0000000LL) return false;
-  return a.pre_scale == nullptr || a.Kp <= kMaxPreKp;
-}
-
-// `a`, `cb` as for launch_convt2x2 (convt2x2.hip); a.w is the [Kp/8][parts][Np][8] bf16 packing of the [Cin, 4 * cb] matrix.
-int launch_convt2x2_split(const ConvArgs& a, int cb, int parts, int cfg, hipStream_t s) {
-  if (parts < 1 || parts > 3) return DH_EINVAL;
+// DH_OK: a layer launch_convt2x2_split runs (a.w aside); DH_EINVAL: arguments that describe no layer; DH_EUNSUPPORTED: a layer
+// the kernel is not built for.  Geometry and alignment only: no pointer is dereferenced, the weight pointer is not looked at.
+int convts_check(const ConvArgs& a, int cb) {
   if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.Cin <= 0 || cb <= 0 || a.Cout != 4 * cb) return DH_EINVAL;
   if (a.Kp % BK != 0 || a.Np % 32 != 0 || a.Kp < a.Cin || a.Np < a.Cout || a.ldx < a.Cin || a.ldy < cb ||
       (a.res1 != nullptr && a.ldr1 < cb))
     return DH_EINVAL;
   const long long M = (long long)a.N * a.H * a.W;
   if (M > 0x7fffffffLL / 4) return DH_EINVAL;                          // 4 M output pixels are indexed in 32 bits per frame row
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!convt2x2_split_eligible(a, cb) || !al16(a.w)) return DH_EUNSUPPORTED;
+  // the LDS-DMA loads move 16 bytes per lane through 32-bit buffer offsets (activations, packed split weight)
+  if (a.Cin % 4 != 0 || a.ldx % 4 != 0 || !al16(a.x)) return DH_EUNSUPPORTED;
+  if (M * a.ldx * 4 > kMaxBufferBytes || (long long)a.Kp * a.Np * 6 > kMaxBufferBytes) return DH_EUNSUPPORTED;
+  return a.pre_scale == nullptr || a.Kp <= kMaxPreKp ? DH_OK : DH_EUNSUPPORTED;
+}
+
+}  // namespace
+
+int convt2x2_split_num_cfgs() { return kNumCfgs; }
+
+// What launch_convt2x2_split accepts, for every `parts` (a binding asks before it packs).  `a` describes the GEMM as for
+// launch_convt2x2.
+bool convt2x2_split_eligible(const ConvArgs& a, int cb) { return convts_check(a, cb) == DH_OK; }
+
+// `a`, `cb` as for launch_convt2x2 (convt2x2.hip); a.w is the [Kp/8][parts][Np][8] bf16 packing of the [Cin, 4 * cb] matrix.
+int launch_convt2x2_split(const ConvArgs& a, int cb, int parts, int cfg, hipStream_t s) {
+  if (parts < 1 || parts > 3) return DH_EINVAL;
+  if (const int rc = convts_check(a, cb); rc != DH_OK) return rc;
+  if (!al16(a.w)) return DH_EUNSUPPORTED;
+  const long long M = (long long)a.N * a.H * a.W;
   const int vec = (cb % 4 == 0) && (a.ldy % 4 == 0) && al16(a.y) && (a.res1 == nullptr || (a.ldr1 % 4 == 0 && al16(a.res1)));
   if (cfg < 0) {
     // the widest tile that still gives every CU a work-group (256 CUs); all tilings sum K in the same order: same bits

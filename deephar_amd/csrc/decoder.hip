@@ -809,7 +809,6 @@ int launch_depth_from_maps(const float* d, int ldd, const float* h, int ldh, flo
 int launch_kronecker(const float* hm, int ldh, const float* x, int ldx, float* f, int ldf, int B, int P, int J,
                      int C, hipStream_t s) {
   if (B <= 0 || P <= 0 || J <= 0 || C <= 0 || B > 65535) return DH_EINVAL;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if (C % 4 == 0 && ldx % 4 == 0 && al16(x)) {
     const dim3 grid((C + 63) / 64, B);
     const int fvec = ldf % 4 == 0 && al16(f);

@@ -83,6 +83,15 @@ struct LdsLimit {
   }
 };
 
+// Shared launch-side predicates.
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+// bytes a buffer descriptor may span: every 32-bit byte offset into it stays below the out-of-range offsets the kernels use
+constexpr long long kMaxBufferBytes = 0xf0000000LL;
+// a 1x1 / stride-1 / unpadded filter ...
+inline bool conv_is_1x1(const ConvArgs& a) { return a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PT == 0 && a.PL == 0; }
+// ... over a map it leaves the size of, with 16-byte channel runs: the pointwise form of the LDS-DMA GEMM family
+inline bool conv_is_pointwise(const ConvArgs& a) { return conv_is_1x1(a) && a.H == a.OH && a.W == a.OW && a.Cin % 4 == 0; }
+
 inline int check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? DH_OK : DH_ELAUNCH;

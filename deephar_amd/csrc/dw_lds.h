@@ -3,6 +3,7 @@
 // tensor and do not depend on each other: one launch runs both, conv_dw_group_kernel).
 #pragma once
 #include "dh_kernels.h"
+#include "lds_dma.h"   // relu4: one integer max per element
 
 namespace dh {
 namespace dwl {
@@ -58,14 +59,6 @@ __device__ __forceinline__ void buf_st4(RSRC rs, int voff, int soff, float4 r) {
   v.x = __float_as_uint(r.x); v.y = __float_as_uint(r.y); v.z = __float_as_uint(r.z); v.w = __float_as_uint(r.w);
   __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, soff, 0);
 #endif
-}
-// relu as one integer max per element (see gemm1x1.hip: relu1)
-__device__ __forceinline__ float dw_relu1(float v) {
-  const int b = __float_as_int(v);
-  return __int_as_float(b > 0 ? b : 0);
-}
-__device__ __forceinline__ float4 dw_relu4(float4 v) {
-  return make_float4(dw_relu1(v.x), dw_relu1(v.y), dw_relu1(v.z), dw_relu1(v.w));
 }
 
 // MAXT / MAXN: load slots per thread for the KS - 1 rows above the first band / for the `rows` new rows of a band
@@ -176,7 +169,7 @@ __device__ __forceinline__ void dwconv_lds_body(const DwArgs& p, const int tw, c
       v = fma4(v, sc, sh);
       if (!((unsigned)(tr - p.PT) < (unsigned)p.H && (unsigned)iw < (unsigned)p.W)) v = zero;
     }
-    if constexpr (RELU) v = dw_relu4(v);
+    if constexpr (RELU) v = relu4(v);
     if (px < (KS - 1) * twh) tile[px * DW_PITCH + q] = v;
   }
   const int strips = tw >> 3;
@@ -198,7 +191,7 @@ __device__ __forceinline__ void dwconv_lds_body(const DwArgs& p, const int tw, c
         v = fma4(v, sc, sh);
         if (!(trow[j] >= 0 && (unsigned)(r0 + KS - 1 - p.PT + trow[j]) < (unsigned)p.H)) v = zero;   // pad AFTER the affine
       }
-      if constexpr (RELU) v = dw_relu4(v);
+      if constexpr (RELU) v = relu4(v);
       int o = loff[j] + shift;
       o = o >= ring_bytes ? o - ring_bytes : o;
       o = loff[j] < 0 ? dump : o;
@@ -251,7 +244,6 @@ struct DwLdsGeom {
   size_t lds;
 };
 inline bool dw_lds_geometry(const DwArgs& a, DwLdsGeom& g) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && al16(a.x) && al16(a.y) && al16(a.w) &&
                    (a.pre_scale == nullptr || (al16(a.pre_scale) && al16(a.pre_shift)));
   if (!(vec && a.KH == a.KW && (a.KW == 5 || a.KW == 3) && a.C % 32 == 0 && a.W >= DW_LDS_MIN_W && a.W % 8 == 0)) return false;

@@ -1,15 +1,16 @@
 // The body of the split-bf16 LDS-DMA GEMM kernels, as TEXT: included inside a __global__ function that provides
 //   template / constexpr values  WM, WN, TM, TN, UP2, RELU, KXK, NS, P, PRE, D2S, K16
 //   variables                    p (const ConvArgs, the KERNEL ARGUMENT itself), epi_vec, cb (D2S: columns per output-pixel block)
-// gemm1x1s.hip (gemm1x1s_kernel: the convolution, PRE = D2S = false) and convt2x2s.hip (convt2x2s_kernel: the transposed 2x2 /
+// gemm1x1s_launch.h (gemm1x1s_kernel: the convolution, PRE = D2S = false) and convt2x2s.hip (convt2x2s_kernel: the transposed 2x2 /
 // stride-2 convolution -- the same main loop in front of the depth-to-space epilogue, D2S, with that layer's BatchNormalization
 // prologue, PRE: scale | shift tables in LDS behind the operand stages, zero beyond K, applied in split8).
 // Text rather than a device function on purpose: behind a function boundary (const ConvArgs& or by value, always inlined) hipcc
 // no longer treats the fields of the kernel argument as wave-uniform everywhere -- the epilogues' scalar buffer offsets then
 // go through readfirstlane loops (74-114 more instructions per kernel, measured on the instantiations of gemm1x1s_p1.hip).
-// K16 (gemm1x1s_ext.hip: K x K with Cin % 16 == 0): the tap-major loop resolves (kh, kw, c0) per 16-channel HALF of the K-step
+// K16 (gemm1x1s_ext_launch.h: K x K with Cin % 16 == 0): the tap-major loop resolves (kh, kw, c0) per 16-channel HALF of the K-step
 // instead of once per step, so a step may hold two taps; LDS layout, fragment reads, split and MFMA stream are those of KXK.
-// Helpers (dma16, lds_rd, split8, mfma_products, ...) are those of gemm1x1s.hip, which must be included first.
+// Helpers: dma16, lds_rd, ... of lds_dma.h and split8, mfma_products, ... of split_bf16.h, which must be included first (with BK of
+// gemm_family.h).
   static_assert(!(PRE && (KXK || UP2 || TM != 1)), "the BN prologue is built for the pipelined pointwise loop");
   static_assert(!(D2S && (KXK || UP2)), "the depth-to-space epilogue follows the plain pointwise main loop");
   static_assert(!K16 || KXK, "per-half taps are a form of the tap-major K x K loop");

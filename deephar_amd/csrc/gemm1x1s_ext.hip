@@ -12,99 +12,12 @@
 //       (K16 of the body), every tiling of the body kernel.
 // A layer the standard rule takes runs the standard kernels under these codes too (launch_gemm1x1_split): the same bits.
 // The packings are those of w_split = 1 / 3 / 4 byte for byte ([Kp/8][P parts][Np][8] bf16, K tap-major, Kp rounded to 32).
-// One translation unit per mode, as gemm1x1s_p2.hip / _p1.hip: this file is the three-part mode, the rule and the dispatch.
-#define DH_CONVT_TU      // (the helpers and the kernel body of gemm1x1s.hip, not its launch side)
-#include <algorithm>
-
-#include "gemm1x1s.hip"
+// One translation unit per mode, as gemm1x1s_p2.hip / _p1.hip: this file is the three-part mode, the rule and the dispatch; the
+// kernel and its launch side are gemm1x1s_ext_launch.h.
+#include "gemm1x1s_ext_launch.h"
 
 namespace dh {
-namespace {
 
-template <int P, int WM, int WN, int TM, int TN, bool RELU, bool KXK, bool PRE, int NS>
-__global__ __launch_bounds__(WM* WN * 64, 2) void gemm1x1s_ext_kernel(const ConvArgs p, const int epi_vec) {
-  constexpr bool UP2 = false, D2S = false, K16 = KXK;
-  constexpr int cb = 0;
-#include "gemm1x1s_body.h"
-}
-
-template <int P, int WM, int WN, int TM, int TN, bool RELU, bool KXK, bool PRE, int NS>
-int launch_ext_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t s) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  constexpr int kStage = NS * (BM * BK + 4 * P * BN * 4), kEpi = WM * WN * 32 * (TN * 32 + 4);
-  constexpr size_t kLds = (size_t)(kStage > kEpi ? kStage : kEpi) * sizeof(float);
-  // PRE: the scale | shift tables sit behind the NS stages (the epilogue slab, when larger, only starts after the K loop)
-  constexpr size_t kMax = PRE ? std::max(kLds, (size_t)(kStage + 2 * kMaxPreKp) * sizeof(float)) : kLds;
-  if constexpr (kMax > 160 * 1024) {
-    return DH_EUNSUPPORTED;            // three stages of the 256-row tiles leave no room for the largest tables
-  } else {
-    static_assert(kMax <= 160 * 1024, "LDS budget");
-    const size_t lds = PRE ? std::max(kLds, (size_t)(kStage + 2 * a.Kp) * sizeof(float)) : kLds;
-    auto kern = gemm1x1s_ext_kernel<P, WM, WN, TM, TN, RELU, KXK, PRE, NS>;
-    if (kMax > 64 * 1024) {
-      static LdsLimit lim;
-      lim.raise((const void*)kern, (int)kMax);
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(NT), lds, s, a, epi);
-    return check_launch();
-  }
-}
-
-template <int P, int WM, int WN, int TM, int TN, int NS = 2>
-int launch_ext_cfg(const ConvArgs& a, int epi, hipStream_t s) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long tiles = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-  if (tiles <= 0 || tiles > 0x7fffffffLL) return DH_EINVAL;
-  const unsigned t = (unsigned)tiles;
-  if (a.y_pool != nullptr && !conv_epilogue_pools_for<WM, TM, false>(a)) return DH_EUNSUPPORTED;
-  if (a.pre_scale != nullptr) {        // (a): the BN prologue exists on the pipelined loop only
-    if constexpr (TM != 1) {
-      return DH_EUNSUPPORTED;
-    } else {
-      return a.pre_relu ? launch_ext_variant<P, WM, WN, TM, TN, true, false, true, NS>(a, epi, t, s)
-                        : launch_ext_variant<P, WM, WN, TM, TN, false, false, true, NS>(a, epi, t, s);
-    }
-  }
-  return a.pre_relu ? launch_ext_variant<P, WM, WN, TM, TN, true, true, false, NS>(a, epi, t, s)
-                    : launch_ext_variant<P, WM, WN, TM, TN, false, true, false, NS>(a, epi, t, s);
-}
-
-// the tilings of gemm1x1s.hip (launch_split_parts), same numbers; the wide tiling (14, 15) is not built for these layers
-template <int P>
-int launch_ext_parts(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  switch (cfg) {
-    case 0: return launch_ext_cfg<P, 2, 2, 2, 3>(a, epi, s);
-    case 1: return launch_ext_cfg<P, 2, 2, 2, 2>(a, epi, s);
-    case 2: return launch_ext_cfg<P, 4, 1, 1, 3>(a, epi, s);
-    case 3: return launch_ext_cfg<P, 4, 1, 1, 2>(a, epi, s);
-    case 4: return launch_ext_cfg<P, 4, 1, 1, 1>(a, epi, s);
-    case 5: return launch_ext_cfg<P, 2, 1, 1, 3>(a, epi, s);
-    case 6: return launch_ext_cfg<P, 2, 1, 1, 2>(a, epi, s);
-    case 7: return launch_ext_cfg<P, 2, 1, 1, 1>(a, epi, s);
-    case 8: return launch_ext_cfg<P, 1, 1, 1, 1>(a, epi, s);
-    case 9: return launch_ext_cfg<P, 8, 1, 1, 3, 3>(a, epi, s);
-    case 10: return launch_ext_cfg<P, 4, 1, 1, 3, 3>(a, epi, s);
-    case 11: return launch_ext_cfg<P, 8, 1, 1, 2, 3>(a, epi, s);
-    case 12: return launch_ext_cfg<P, 4, 2, 1, 3, 2>(a, epi, s);
-    case 13: return launch_ext_cfg<P, 4, 2, 2, 3, 2>(a, epi, s);
-    case 14:
-    case 15: return DH_EUNSUPPORTED;
-  }
-  return DH_EINVAL;
-}
-
-}  // namespace
-
-#ifndef DH_SPLIT_PARTS
-#define DH_SPLIT_PARTS 3
-#endif
-
-#if DH_SPLIT_PARTS == 2
-int launch_gemm1x1_split_ext_p2(const ConvArgs& a, int cfg, int epi, hipStream_t s) { return launch_ext_parts<2>(a, cfg, epi, s); }
-#elif DH_SPLIT_PARTS == 1
-int launch_gemm1x1_split_ext_p1(const ConvArgs& a, int cfg, int epi, hipStream_t s) { return launch_ext_parts<1>(a, cfg, epi, s); }
-#else
 bool gemm1x1_eligible(const ConvArgs& a);
 int launch_gemm1x1_split(const ConvArgs& a, int cfg, int epi, hipStream_t s);
 int launch_gemm1x1_split_ext_p2(const ConvArgs& a, int cfg, int epi, hipStream_t s);
@@ -123,15 +36,12 @@ int ext_class(const ConvArgs& a0) {
   if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.OH <= 0 || a.OW <= 0 || a.Cin <= 0 || a.Cout <= 0 || a.KH < 1 || a.KW < 1) return 0;
   if (a.K != a.KH * a.KW * a.Cin || a.Kp % BK != 0 || a.Kp < a.K || a.Np % 32 != 0 || a.Np < a.Cout || a.ldx < a.Cin) return 0;
   if (a.x_u8 || a.up2 || a.x_resample || conv_is_skinny(a) || conv_stem_eligible(a)) return 0;
-  if (a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x) & 15) != 0) return 0;
+  if (a.ldx % 4 != 0 || !al16(a.x)) return 0;
   // 32-bit byte offsets into the buffer descriptors
-  if ((long long)a.N * a.H * a.W * a.ldx * 4 > 0xf0000000LL || (long long)a.Kp * a.Np * 6 > 0xf0000000LL) return 0;
-  const bool pointwise = a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PT == 0 && a.PL == 0 && a.H == a.OH &&
-                         a.W == a.OW && a.Cin % 4 == 0;
+  if ((long long)a.N * a.H * a.W * a.ldx * 4 > kMaxBufferBytes || (long long)a.Kp * a.Np * 6 > kMaxBufferBytes) return 0;
   if (a.pre_scale != nullptr || a.pre_shift != nullptr)      // a prologue needs both tables, and LDS room for them
-    return pointwise && a.pre_scale != nullptr && a.pre_shift != nullptr && a.Kp <= kMaxPreKp ? 1 : 0;
-  const bool one_by_one = a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PT == 0 && a.PL == 0;
-  return !one_by_one && a.Cin % 16 == 0 && a.SH >= 1 && a.SW >= 1 && a.PT >= 0 && a.PL >= 0 ? 2 : 0;
+    return conv_is_pointwise(a) && a.pre_scale != nullptr && a.pre_shift != nullptr && a.Kp <= kMaxPreKp ? 1 : 0;
+  return !conv_is_1x1(a) && a.Cin % 16 == 0 && a.SH >= 1 && a.SW >= 1 && a.PT >= 0 && a.PL >= 0 ? 2 : 0;
 }
 }  // namespace
 
@@ -142,7 +52,7 @@ bool gemm1x1_split_wide_eligible(const ConvArgs& a) { return gemm1x1_split_eligi
 int launch_gemm1x1_split_wide(const ConvArgs& a0, int cfg, int epi, hipStream_t s) {
   const int base = conv_split_wide_base(a0.w_split);
   if (base == 0) return DH_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(a0.w) & 15) != 0) return DH_EUNSUPPORTED;
+  if (!al16(a0.w)) return DH_EUNSUPPORTED;
   ConvArgs a = a0;
   a.w_split = base;
   if (gemm1x1_split_eligible(a)) {     // a layer of the standard scope: the standard kernels, the same bits
@@ -158,6 +68,4 @@ int launch_gemm1x1_split_wide(const ConvArgs& a0, int cfg, int epi, hipStream_t 
   }
   return DH_EINVAL;
 }
-#endif
-
 }  // namespace dh

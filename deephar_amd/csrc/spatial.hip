@@ -344,8 +344,6 @@ inline unsigned grid_for(long long total, int block = 256) {
   return (unsigned)g;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <int KS, int NT, int MAXT, int MAXN, bool AFF, bool RELU>
 int launch_dw_lds_variant(const DwArgs& a, int tw, int rows, unsigned blocks, size_t lds, hipStream_t s) {
   auto kern = dwconv_lds_kernel<KS, NT, MAXT, MAXN, AFF, RELU>;

@@ -87,6 +87,25 @@ def test_launcher_rules_restated_still_stand_in_the_source():
         assert gsrc.count('case %d: return launch_cfg<%d, %d, %d, %d>(a, epi, s);' % (i, wm, wn, tm, tn)) == 1
 
 
+def test_no_source_includes_a_source_and_the_split_tilings_stand_once():
+    """The kernel sources share code through headers only, and the split-bf16 tilings -- stated once, in gemm_family.h, for the
+    standard and the extended scope -- are the ones the benchmark names its kernels by."""
+    csrc = os.path.join(ROOT, 'deephar_amd', 'csrc')
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h'))}
+    for fname, text in texts.items():
+        assert not re.search(r'#\s*include\s*["<][^">]*\.hip[">]', text), '%s includes a source' % fname
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    tiles = {int(c): (tuple(int(v) for v in t.split(',')[:4]), int((t.split(',') + ['2'])[4]))
+             for c, t in re.findall(r'case (\d+): return f\(SplitTile<([\d, ]+)>\{\}\);', texts['gemm_family.h'])}
+    wide = {int(c): int(wm) for c, wm in re.findall(r'case (\d+): return f\(SplitWideTile<(\d+)>\{\}\);', texts['gemm_family.h'])}
+    assert tiles == bench.SPLIT_TILES and wide == bench.SPLIT_WIDE
+    assert sorted(tiles) + sorted(wide) == list(range(16))
+    rows = [(f, m) for f, text in texts.items() for m in re.findall(r'Split(?:Wide)?Tile<[\d, ]+>', text)]
+    assert len(rows) == 16 and all(f == 'gemm_family.h' for f, _ in rows), rows     # nowhere else, and none twice
+
+
 def test_case_tables_reach_every_path_of_the_launcher():
     reached, per = set(), {}
     for case, sname, lay, tabs, a in _launches():
