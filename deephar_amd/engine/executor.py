@@ -6,16 +6,16 @@ torch compute and no CPU fallback.  The launch sequence of a bound plan is captu
 (dh_graph_*), so steady-state `predict` costs one graph launch per batch instead of ~300 kernel launches.
 """
 import ctypes as C
-import functools
 import os
 
 import numpy as np
 
 from .. import _lib
-from . import packing
+from . import binding, packing
+from .binding import grid_x, grid_depth      # noqa: F401  (their home is the binder; functional.py and the tests look here)
 
-SPLIT_CODES = {'bf16x3': 1, 'bf16x2': 3, 'bf16': 4}      # Plan.gemm_precision -> dh_conv_args.w_split (packing.SPLIT_PARTS)
-WIDE_SPLIT_CODES = {'bf16x3': 5, 'bf16x2': 6, 'bf16': 7}  # the same under Plan.gemm_scope == 'extended' (packing.WIDE_SPLIT_PARTS)
+SPLIT_CODES = packing.LAYOUT_CODES['standard']        # Plan.gemm_precision -> dh_conv_args.w_split (packing.LAYOUTS)
+WIDE_SPLIT_CODES = packing.LAYOUT_CODES['extended']   # the same under Plan.gemm_scope == 'extended'
 
 BN_EPS = 1e-3  # keras BatchNormalization default epsilon (SURVEY.md A.3)
 
@@ -46,24 +46,36 @@ class WeightStore:
                                'deephar_amd.weights.init_synthetic(model) before predict' % p.key)
         return p.value
 
-    def conv_weight(self, p, split=0):
-        """split = dh_conv_args.w_split: 0 fp32 tap-major, 1 / 3 / 4 the split-bf16 packing with three / two / one part,
-        2 fp32 chunk-major (halo-resident K x K kernel); different packings of one Param are kept side by side when
-        several are in use.  5 / 6 / 7 (the extended scope) are the bytes of 1 / 3 / 4 and share their tensor."""
-        split = packing.WIDE_SPLIT_BASE.get(int(split), int(split))
-        key = (id(p), int(split))
-        ent = self.conv.get(key)
-        if ent is None or ent[3] != p.version:
-            packer = {0: packing.pack_conv, 2: packing.pack_conv_halo}.get(int(split)) or \
-                functools.partial(packing.pack_conv_split, parts=packing.SPLIT_PARTS[int(split)])
-            packed, kp, np_ = packer(self._require(p))
+    def _entry(self, table, key, version, make):
+        """table[key] = (device tensors..., further fields..., version): created from make() -> (host arrays, further fields),
+        or -- when the version moved -- copied into the tensors already there (pointers stay valid)."""
+        ent = table.get(key)
+        if ent is None or ent[-1] != version:
+            arrays, extra = make()
             if ent is None:
-                ent = (self._dev(packed), kp, np_, p.version)
+                tensors = tuple(self._dev(a) for a in arrays)
             else:
-                ent[0].copy_(self._dev(packed))
-                ent = (ent[0], kp, np_, p.version)
-            self.conv[key] = ent
-        return ent[0], ent[1], ent[2]
+                tensors = ent[:len(arrays)]
+                for t, a in zip(tensors, arrays):
+                    t.copy_(self._dev(a))
+            ent = table[key] = tensors + tuple(extra) + (version,)
+        return ent
+
+    def _packed(self, key, p, pack):
+        def make():
+            w, kp, np_ = pack(self._require(p))
+            return (w,), (kp, np_)
+        return self._entry(self.conv, key, p.version, make)[:3]
+
+    def conv_weight(self, p, split=0):
+        """split = dh_conv_args.w_split (packing.LAYOUTS): 0 fp32 tap-major, 1 / 3 / 4 the split-bf16 packing with three / two /
+        one part, 2 fp32 chunk-major (halo-resident K x K kernel); different packings of one Param are kept side by side when
+        several are in use.  5 / 6 / 7 (the extended scope) are the bytes of 1 / 3 / 4 and share their tensor."""
+        split = packing.LAYOUTS[int(split)].base
+        parts = packing.LAYOUTS[split].parts
+        if parts:
+            return self._packed((id(p), split), p, lambda w: packing.pack_conv_split(w, parts=parts))
+        return self._packed((id(p), split), p, packing.pack_conv_halo if split == 2 else packing.pack_conv)
 
     CONVT = 'convt'       # packing key of a Conv2DTranspose kernel in `conv` (beside the dh_conv_args.w_split codes)
 
@@ -72,29 +84,13 @@ class WeightStore:
         GEMM (packing.pack_convt); kept in `conv` like every packed GEMM weight.  split = 0: fp32; 1 / 3 / 4 (the codes of
         dh_conv_args.w_split): the split-bf16 packing with three / two / one part, kept beside the fp32 one."""
         key = (id(p), self.CONVT if not split else (self.CONVT, int(split)))
-        ent = self.conv.get(key)
-        if ent is None or ent[3] != p.version:
-            packed, kp, np_ = packing.pack_convt(self._require(p), parts=packing.SPLIT_PARTS[int(split)] if split else None)
-            if ent is None:
-                ent = (self._dev(packed), kp, np_, p.version)
-            else:
-                ent[0].copy_(self._dev(packed))
-                ent = (ent[0], kp, np_, p.version)
-            self.conv[key] = ent
-        return ent[0], ent[1], ent[2]
+        return self._packed(key, p, lambda w: packing.pack_convt(w, parts=packing.LAYOUTS[int(split)].parts))
 
     def dw_weight(self, p):
-        ent = self.dw.get(id(p))
-        if ent is None or ent[1] != p.version:
+        def flat():
             w = self._require(p)
-            flat = np.ascontiguousarray(w.reshape(w.shape[0] * w.shape[1], w.shape[2]))
-            if ent is None:
-                ent = (self._dev(flat), p.version)
-            else:
-                ent[0].copy_(self._dev(flat))
-                ent = (ent[0], p.version)
-            self.dw[id(p)] = ent
-        return ent[0]
+            return (np.ascontiguousarray(w.reshape(w.shape[0] * w.shape[1], w.shape[2])),), ()
+        return self._entry(self.dw, id(p), p.version, flat)[0]
 
     def _bn_host(self, layer):
         byrole = {p.role: self._require(p) for p in layer.params}
@@ -107,24 +103,14 @@ class WeightStore:
         """BatchNormalization inference as y = x*scale + shift (fp32, like tf.nn.batch_normalization).  A
         planner.ConcatAffine (the affine behind a horizontally merged convolution, rule R10c) gives the per-column scale /
         shift of its parts side by side, identity (1, 0) for a part without a BatchNormalization."""
-        vers = tuple(p.version for p in layer.params)
-        ent = self.bn.get(id(layer))
-        if ent is None or ent[2] != vers:
-            if hasattr(layer, 'parts'):
-                pieces = [self._bn_host(l) if l is not None else (np.ones(c, np.float32), np.zeros(c, np.float32))
-                          for c, l in layer.parts]
-                inv = np.concatenate([a for a, _ in pieces]).astype(np.float32)
-                shift = np.concatenate([b for _, b in pieces]).astype(np.float32)
-            else:
-                inv, shift = self._bn_host(layer)
-            if ent is None:
-                ent = (self._dev(inv), self._dev(shift), vers)
-            else:
-                ent[0].copy_(self._dev(inv))
-                ent[1].copy_(self._dev(shift))
-                ent = (ent[0], ent[1], vers)
-            self.bn[id(layer)] = ent
-        return ent[0], ent[1]
+        def host():
+            if not hasattr(layer, 'parts'):
+                return self._bn_host(layer), ()
+            pieces = [self._bn_host(l) if l is not None else (np.ones(c, np.float32), np.zeros(c, np.float32))
+                      for c, l in layer.parts]
+            return (np.concatenate([a for a, _ in pieces]).astype(np.float32),
+                    np.concatenate([b for _, b in pieces]).astype(np.float32)), ()
+        return self._entry(self.bn, id(layer), tuple(p.version for p in layer.params), host)[:2]
 
     def constant(self, key, make):
         t = self.const.get(key)
@@ -132,11 +118,6 @@ class WeightStore:
             t = self._dev(make())
             self.const[key] = t
         return t
-
-
-def grid_x(w):
-    """float32 x grid of utils/math.py:6-19 (np.linspace(0,1,W) stored into a float32 array)."""
-    return np.linspace(0.0, 1.0, num=w).astype(np.float32)
 
 
 def normalization_lut(channels, channel_power=1):
@@ -156,12 +137,6 @@ def normalization_lut(channels, channel_power=1):
         v *= 2.
         lut[c] = v
     return lut
-
-
-def grid_depth(d):
-    """layers.py:141-143: linspace(1/(2D), 1-1/(2D), D) stored in float32 Conv1D weights."""
-    s = 1 / (2 * d)
-    return np.linspace(s, 1 - s, num=d).astype(np.float32)
 
 
 class _InputStep:
@@ -225,26 +200,6 @@ class BoundPlan:
         self.paired = []          # (index of the paired launch, index of the launch it absorbed): _pair_skinny_convs
         self.absorbed = {}        # index of a grouped / paired launch -> the Step whose work it also does
 
-    def weight_layout(self, args):
-        """dh_conv_args.w_split of a conv step: 1 / 3 / 4 = split-bf16 (plan.gemm_precision == 'bf16x3' / 'bf16x2' / 'bf16'
-        and the library takes the layer: dh_conv2d_split_eligible, one rule for the three), 2 = fp32 chunk-major for the halo-resident K x K kernel
-        (dh_conv2d_halo_eligible: a rule on the per-frame geometry), else 0.  The LIBRARY decides, asked with the launch's
-        own argument struct before the weights are packed -- a layer is never bound with a packing its launch rejects.
-        Under plan.gemm_scope == 'extended' the wider rule is asked instead (dh_conv2d_split_wide_eligible) and the layer is
-        bound with the extended scope's code, 5 / 6 / 7; a layer it refuses falls to halo / fp32 as under 'standard'."""
-        mode = getattr(self.plan, 'gemm_precision', 'f32')
-        if getattr(self.plan, 'gemm_scope', 'standard') == 'extended':
-            code = WIDE_SPLIT_CODES.get(mode)
-            if code and self.lib.dh_conv2d_split_wide_eligible(C.byref(args)):
-                return code
-        else:
-            code = SPLIT_CODES.get(mode)
-            if code and self.lib.dh_conv2d_split_eligible(C.byref(args)):
-                return code
-        if self.plan.rules.halo_conv and self.lib.dh_conv2d_halo_eligible(C.byref(args)):
-            return 2
-        return 0
-
     # ---- views -------------------------------------------------------------------------------------------
     def ptr(self, v):
         return self.base + 4 * (v.buf.offset * self.n + v.coff)
@@ -261,243 +216,41 @@ class BoundPlan:
                 strides[i] = strides[i + 1] * shape[i + 1]
         return torch.as_strided(self.arena, shape, strides, v.buf.offset * self.n + v.coff)
 
-    # ---- binding -----------------------------------------------------------------------------------------
+    # ---- binding: the env of engine/binding.py over the arena and the WeightStore, and the part that needs a device ----------
+    def affine(self, layer):
+        sc, sh = self.store.bn_affine(layer)
+        return sc.data_ptr(), sh.data_ptr()
+
+    def constant(self, key, make):
+        return self.store.constant(key, make).data_ptr()
+
+    def dw_weight(self, p):
+        return self.store.dw_weight(p).data_ptr()
+
+    def u8_input(self, buf):
+        ent = (self.u8 or {}).get(id(buf))
+        return (ent[0].data_ptr(), ent[1].data_ptr()) if ent is not None and ent[2] else None
+
     def _bind(self, s):
-        lib, n, k = self.lib, self.n, s.kind
-        a = s.attrs
-        P = self.ptr
-
-        def opt(role, d=s.ins):
-            v = d.get(role)
-            return P(v) if v is not None else None
-
-        if k == 'conv':
-            x, y = s.ins['x'], s.outs['y']
-            args = _lib.ConvArgs()
-            args.x, args.y = P(x), P(y)
-            if 'pre_bn' in s.params:
-                sc, sh = self.store.bn_affine(s.params['pre_bn'])
-                args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
-            if 'post_bn' in s.params or 'post_affine' in s.params:
-                sc, sh = self.store.bn_affine(s.params.get('post_bn') or s.params['post_affine'])
-                args.post_scale, args.post_shift = sc.data_ptr(), sh.data_ptr()
-            up = 2 if a['up2'] else 1
-            args.N = n * x.lead(3)
-            args.H, args.W, args.Cin, args.ldx = x.shape[-3], x.shape[-2], x.C, x.ld
-            sg = a.get('seg')                          # planner rule R14: x = [MaxPooling2D(x) | x2], read in place
-            if sg is not None:                         # (H, W: the extent the convolution sees; Cin: both segments)
-                args.H, args.W, args.Cin = x.shape[-3] // sg['pool_sh'], x.shape[-2] // 2, a['Cin']
-            rs = a.get('x_resample', 0)                # planner rule R12: x is stored at another resolution than the conv sees
-            if rs:
-                args.x_resample = rs
-                args.H, args.W = (2 * x.shape[-3], 2 * x.shape[-2]) if rs == 1 else (x.shape[-3] // 2, x.shape[-2] // 2)
-            args.OH, args.OW, args.Cout, args.ldy = y.shape[-3] // up, y.shape[-2] // up, a['Cout'], y.ld
-            args.KH, args.KW, args.SH, args.SW, args.PT, args.PL = a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']
-            kp_np = (C.c_int(), C.c_int())
-            _lib.check(lib.dh_conv2d_packed_dims(a['kh'], a['kw'], args.Cin, a['Cout'], C.byref(kp_np[0]), C.byref(kp_np[1])))
-            args.K, args.Kp, args.Np = a['K'], kp_np[0].value, kp_np[1].value
-            r1, r2 = s.ins.get('res1'), s.ins.get('res2')
-            if r1 is not None:
-                args.res1, args.ldr1 = P(r1), r1.ld
-            if r2 is not None:
-                args.res2, args.ldr2 = P(r2), r2.ld
-            args.pre_relu, args.post_relu, args.up2 = a['pre_relu'], a['post_relu'], a['up2']
-            args.res2_down = a.get('res2_down', 0)
-            yp = s.outs.get('ypool')
-            if yp is not None:                         # planner rule R7: the 2x2 max-pooled second output
-                args.y_pool, args.ldyp = P(yp), yp.ld
-            if self.u8 is not None and id(x.buf) in self.u8 and self.u8[id(x.buf)][2]:
-                buf, lut, _ = self.u8[id(x.buf)]
-                args.x, args.in_lut, args.x_u8 = buf.data_ptr(), lut.data_ptr(), 1
-            a['x_u8'] = int(args.x_u8)                 # (read by bench.py to name the kernel)
-            split = self.weight_layout(args)           # every field but w / w_split is final here
-            wt, kp, np_ = self.store.conv_weight(s.params['w'], split=split)
-            assert (kp, np_) == (args.Kp, args.Np)
-            args.w, args.w_split = wt.data_ptr(), int(split)
-            a['w_split'] = int(split)                  # (read by bench.py to name the kernel)
-            self._keep.append(args)
-            if sg is not None:
-                seg = _lib.ConvSeg()
-                x2 = s.ins.get('x2')
-                if x2 is not None:
-                    seg.x2, seg.ldx2 = P(x2), x2.ld
-                seg.c_split, seg.pool_sh = sg['c_split'], sg['pool_sh']
-                self._keep.append(seg)
-                self.calls.append((lib.dh_conv2d_seg_f32, (C.byref(args), C.byref(seg)), s))
-                return
-            self.calls.append((lib.dh_conv2d_f32, (C.byref(args), a.get('tile_cfg', -1)), s))
-        elif k == 'dwconv' and (a.get('sh', 1), a.get('sw', 1)) != (1, 1):
-            x, y = s.ins['x'], s.outs['y']             # the depthwise half of a strided SeparableConv2D
-            args = _lib.DwsArgs()
-            args.x, args.w, args.y = P(x), self.store.dw_weight(s.params['w']).data_ptr(), P(y)
-            if 'pre_bn' in s.params:
-                sc, sh = self.store.bn_affine(s.params['pre_bn'])
-                args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
-            args.N, args.H, args.W, args.C = n * x.lead(3), x.shape[-3], x.shape[-2], x.C
-            args.OH, args.OW, args.ldx, args.ldy = y.shape[-3], y.shape[-2], x.ld, y.ld
-            args.KH, args.KW, args.SH, args.SW, args.PT, args.PL = a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']
-            args.pre_relu = a['pre_relu']
-            self._keep.append(args)
-            self.calls.append((lib.dh_dwconv2d_strided_f32, (C.byref(args),), s))
-        elif k == 'convtranspose':
-            x, y = s.ins['x'], s.outs['y']             # Conv2DTranspose((2, 2), strides=(2, 2))
-            args = _lib.ConvtArgs()
-            args.x, args.y = P(x), P(y)
-            if 'pre_bn' in s.params:
-                sc, sh = self.store.bn_affine(s.params['pre_bn'])
-                args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
-            r1 = s.ins.get('res1')
-            if r1 is not None:
-                args.res, args.ldr = P(r1), r1.ld
-            args.N, args.H, args.W, args.Cin, args.ldx = n * x.lead(3), x.shape[-3], x.shape[-2], x.C, x.ld
-            kp_np = (C.c_int(), C.c_int())
-            _lib.check(lib.dh_conv2d_packed_dims(1, 1, x.C, 4 * a['Cout'], C.byref(kp_np[0]), C.byref(kp_np[1])))
-            args.Cout, args.ldy, args.Kp, args.Np = a['Cout'], y.ld, kp_np[0].value, kp_np[1].value
-            args.pre_relu, args.post_relu = a['pre_relu'], a['post_relu']
-            # plan.gemm_precision: the split-bf16 form when the library takes the layer (one rule for the three modes, asked
-            # with the final argument struct BEFORE the weights are packed, as weight_layout does for convolutions)
-            split = SPLIT_CODES.get(getattr(self.plan, 'gemm_precision', 'f32'), 0)
-            if split and not lib.dh_conv2d_transpose2x2_split_eligible(C.byref(args)):
-                split = 0
-            wt, kp, np_ = self.store.convt_weight(s.params['w'], split=split)
+        """binding.bind fills the launch; here the library picks the weight's packing and the store supplies it."""
+        name, structs, scalars = binding.bind(s, self.n, self)
+        if s.kind in ('conv', 'convtranspose'):
+            args = structs[0]                          # every field but w / w_split is final here
+            if s.kind == 'conv':
+                s.attrs['x_u8'] = int(args.x_u8)       # (read by bench.py to name the kernel)
+                split = binding.weight_layout(self.lib, self.plan, args)
+                wt, kp, np_ = self.store.conv_weight(s.params['w'], split=split)
+                args.w_split = int(split)
+            else:
+                split = binding.convt_weight_layout(self.lib, self.plan, args)
+                wt, kp, np_ = self.store.convt_weight(s.params['w'], split=split)
+                if split:
+                    name, scalars = 'dh_conv2d_transpose2x2_split_f32', [packing.SPLIT_PARTS[split]] + scalars
             assert (kp, np_) == (args.Kp, args.Np)
             args.w = wt.data_ptr()
-            a['w_split'] = int(split)                  # 1 / 3 / 4 as for convolutions, 0: the fp32 kernel
-            self._keep.append(args)
-            if split:
-                self.calls.append((lib.dh_conv2d_transpose2x2_split_f32,
-                                   (C.byref(args), packing.SPLIT_PARTS[split], a.get('tile_cfg', -1)), s))
-            else:
-                self.calls.append((lib.dh_conv2d_transpose2x2_f32, (C.byref(args), a.get('tile_cfg', -1)), s))
-        elif k == 'dwconv':
-            x, y = s.ins['x'], s.outs['y']
-            args = _lib.DwArgs()
-            args.x, args.w, args.y = P(x), self.store.dw_weight(s.params['w']).data_ptr(), P(y)
-            if 'pre_bn' in s.params:
-                sc, sh = self.store.bn_affine(s.params['pre_bn'])
-                args.pre_scale, args.pre_shift = sc.data_ptr(), sh.data_ptr()
-            args.N, args.H, args.W, args.C = n * y.lead(3), y.shape[-3], y.shape[-2], x.C      # (up_in: x is at half resolution)
-            args.ldx, args.ldy = x.ld, y.ld
-            args.KH, args.KW, args.PT, args.PL, args.pre_relu = a['kh'], a['kw'], a['pt'], a['pl'], a['pre_relu']
-            args.up_in = a.get('up_in', 0)
-            self._keep.append(args)
-            self.calls.append((lib.dh_dwconv2d_f32, (C.byref(args),), s))
-        elif k == 'pool':
-            x, y = s.ins['x'], s.outs['y']
-            args = _lib.PoolArgs()
-            args.x, args.y = P(x), P(y)
-            args.N, args.H, args.W, args.C, args.ldx = n * x.lead(3), x.shape[-3], x.shape[-2], x.C, x.ld
-            args.OH, args.OW, args.ldy = y.shape[-3], y.shape[-2], y.ld
-            args.KH, args.KW, args.SH, args.SW, args.PT, args.PL = a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']
-            args.mode = a.get('mode', 0)
-            self._keep.append(args)
-            self.calls.append((lib.dh_pool2d_f32, (C.byref(args),), s))
-        elif k == 'upsample_add':
-            b, y = s.ins['b'], s.outs['y']
-            av = s.ins.get('a')
-            self.calls.append((lib.dh_upsample2x_add_f32,
-                               (P(av) if av is not None else None, av.ld if av is not None else 0, P(b), b.ld,
-                                P(y), y.ld, n * y.lead(3), y.shape[-3], y.shape[-2], y.C), s))
-        elif k == 'eltwise':
-            av, y = s.ins['a'], s.outs['y']
-            args = _lib.EltArgs()
-            args.a, args.y, args.lda, args.ldy = P(av), P(y), av.ld, y.ld
-            bv, cv = s.ins.get('b'), s.ins.get('c')
-            if bv is not None:
-                args.b, args.ldb = P(bv), bv.ld
-            if cv is not None:
-                args.c, args.ldc = P(cv), cv.ld
-            if 'bn' in s.params:
-                sc, sh = self.store.bn_affine(s.params['bn'])
-                args.scale, args.shift = sc.data_ptr(), sh.data_ptr()
-            elif 'scale_const' in a:
-                kc, cc = a['scale_const'], av.C
-                args.scale = self.store.constant(('const', kc, cc), lambda: np.full(cc, kc, np.float32)).data_ptr()
-                args.shift = self.store.constant(('const', 0.0, cc), lambda: np.zeros(cc, np.float32)).data_ptr()
-            args.npix, args.C = n * av.npix, av.C
-            args.relu, args.op, args.bcast_b = a.get('relu', 0), a.get('op', 0), a.get('bcast_b', 0)
-            self._keep.append(args)
-            self.calls.append((lib.dh_eltwise_f32, (C.byref(args),), s))
-        elif k == 'sam':
-            h = s.ins['h']
-            H, W = h.shape[-3], h.shape[-2]
-            args = _lib.SamArgs()
-            args.h = P(h)
-            args.gx = self.store.constant(('gx', W), lambda: grid_x(W)).data_ptr()
-            args.gy = self.store.constant(('gx', H), lambda: grid_x(H)).data_ptr()
-            o = s.outs
-            if o.get('xy') is not None:
-                args.xy, args.ldxy = P(o['xy']), o['xy'].ld
-            if o.get('conf_raw') is not None:
-                args.conf_raw, args.ldcr = P(o['conf_raw']), o['conf_raw'].ld
-            if o.get('conf_prob') is not None:
-                args.conf_prob, args.ldcp = P(o['conf_prob']), o['conf_prob'].ld
-            if o.get('prob') is not None:
-                args.prob, args.ldp = P(o['prob']), o['prob'].ld
-            if o.get('gmax') is not None:
-                assert o['gmax'].dense
-                args.gmax = P(o['gmax'])
-            args.F, args.H, args.W, args.C, args.ldh = n * h.lead(3), H, W, h.C, h.ld
-            args.alpha, args.conf_scale = a['alpha'], a['conf_scale']
-            args.xy_times_conf = a.get('xy_times_conf', 0)
-            self._keep.append(args)
-            self.calls.append((lib.dh_softargmax2d_f32, (C.byref(args),), s))
-        elif k == 'sam_ctx':
-            h, y = s.ins['h'], s.outs['y']
-            H, W = h.shape[-3], h.shape[-2]
-            args = _lib.SamArgs()
-            args.h = P(h)
-            args.gx = self.store.constant(('gx', W), lambda: grid_x(W)).data_ptr()
-            args.gy = self.store.constant(('gx', H), lambda: grid_x(H)).data_ptr()
-            cr = s.outs.get('conf_raw')
-            if cr is not None:
-                args.conf_raw, args.ldcr = P(cr), cr.ld
-            args.F, args.H, args.W, args.C, args.ldh = n * h.lead(3), H, W, h.C, h.ld
-            args.alpha, args.conf_scale = a['sam_alpha'], a['conf_scale']
-            self._keep.append(args)
-            self.calls.append((lib.dh_softargmax2d_context_f32,
-                               (C.byref(args), a['J'], a['nctx'], a['alpha'], P(y), y.ld), s))
-        elif k == 'context_agg':
-            ys, y = s.ins['ys'], s.outs['y']
-            self.calls.append((lib.dh_context_aggregation_f32,
-                               (P(ys), P(s.ins['yc']), P(s.ins['pc']), P(y), n * ys.lead(2), ys.shape[-2],
-                                a['nctx'], a['alpha'], y.ld), s))
-        elif k == 'depth_means':
-            h = s.ins['h']
-            self.calls.append((lib.dh_depth_means_f32,
-                               (P(h), h.ld, opt('hxy', s.outs), opt('hz', s.outs), n * h.lead(3),
-                                h.shape[-3] * h.shape[-2], a['D'], a['J']), s))
-        elif k == 'softargmax1d':
-            hz = s.ins['hz']
-            D, J = hz.shape[-2], hz.shape[-1]
-            grid = self.store.constant(('gd', D), lambda: grid_depth(D))
-            z = s.outs.get('z')
-            self.calls.append((lib.dh_softargmax1d_f32,
-                               (P(hz), grid.data_ptr(), P(z) if z is not None else None,
-                                z.ld if z is not None else 1, opt('vz', s.outs), n * hz.lead(2), D, J), s))
-        elif k == 'kronecker':
-            hm, x, y = s.ins['hm'], s.ins['x'], s.outs['y']
-            self.calls.append((lib.dh_kronecker_f32,
-                               (P(hm), hm.ld, P(x), x.ld, P(y), y.ld, n * hm.lead(3),
-                                hm.shape[-3] * hm.shape[-2], hm.C, x.C), s))
-        elif k == 'globalmaxmin':
-            x, y = s.ins['x'], s.outs['y']
-            self.calls.append((lib.dh_global_maxmin_softmax_f32,
-                               (P(x), x.ld, P(y), n * x.lead(3), x.shape[-3] * x.shape[-2], x.C, a['softmax']), s))
-        elif k == 'copy':
-            x, y = s.ins['x'], s.outs['y']
-            self.calls.append((lib.dh_copy_channels_f32, (P(x), x.ld, P(y), y.ld, n * x.npix, x.C), s))
-        elif k == 'zeropad':
-            x, y = s.ins['x'], s.outs['y']
-            self.calls.append((lib.dh_zeropad2d_f32,
-                               (P(x), P(y), n * x.lead(3), x.shape[-3], x.shape[-2], x.C, y.shape[-3],
-                                y.shape[-2], a.get('pt', 0), a.get('pl', 0)), s))
-        elif k == 'depthsum':
-            d, h, z = s.ins['d'], s.ins['h'], s.outs['z']
-            self.calls.append((lib.dh_depth_from_maps_f32,
-                               (P(d), d.ld, P(h), h.ld, P(z), z.ld, n * d.lead(3), d.shape[-3] * d.shape[-2], d.C), s))
-        else:
-            raise NotImplementedError('no binding for step kind %r' % k)
+            s.attrs['w_split'] = int(split)            # (read by bench.py to name the kernel; convtranspose: 0 = the fp32 kernel)
+        self._keep.extend(structs)
+        self.calls.append((getattr(self.lib, name), tuple(C.byref(st) for st in structs) + tuple(scalars), s))
 
     # ---- execution -----------------------------------------------------------------------------------------
     def _side_streams(self, main_ptr=None):
@@ -723,18 +476,6 @@ class BoundPlan:
         _lib.check(self.lib.dh_graph_launch(self.graph, stream_ptr), 'graph launch')
 
     # ---- autotuning of the conv tiling -------------------------------------------------------------------
-    @staticmethod
-    def _conv_signature(step):
-        a, x, y = step.attrs, step.ins['x'], step.outs['y']
-        r1, r2 = step.ins.get('res1'), step.ins.get('res2')
-        # the 16-byte alignment of every view decides which kernels / epilogues are eligible (gemm1x1_eligible, the
-        # vector epilogue), so it is part of the identity of a tuned shape -- as are padding and the output size
-        align = (x.coff % 4, y.coff % 4, r1.coff % 4 if r1 is not None else 0, r2.coff % 4 if r2 is not None else 0,
-                 r1.ld % 4 if r1 is not None else 0, r2.ld % 4 if r2 is not None else 0)
-        return (x.lead(3), x.shape[-3], x.shape[-2], x.C, x.ld, y.ld, a['Cout'], a['kh'], a['kw'], a['sh'],
-                a['sw'], a['pre_relu'], a['post_relu'], a['up2'], 'res1' in step.ins, 'res2' in step.ins,
-                'pre_bn' in step.params, 'post_bn' in step.params or 'post_affine' in step.params, a['pt'], a['pl'], y.shape[-3], y.shape[-2], a.get('res2_down', 0), 'ypool' in step.outs) + align
-
     def autotune(self, stream_ptr, table=None, reps=3):
         """Time every tile configuration of dh_conv2d_f32 for each distinct conv shape of this bound plan
         (HIP events on the launch stream) and keep the fastest.  All configurations sum K in the same order,
@@ -754,8 +495,8 @@ class BoundPlan:
                 continue
             ncfg = ncfgs[step.kind]
             cargs = args[0]._obj
-            sig = (self.n, step.kind) + self._conv_signature(step) + ((('u8',) if cargs.x_u8 else ())) + \
-                ((({1: 'bf16x3', 2: 'halo', 3: 'bf16x2', 4: 'bf16', 5: 'bf16x3', 6: 'bf16x2', 7: 'bf16'}[cargs.w_split],) if cargs.w_split else ()))
+            sig = (self.n, step.kind) + binding.conv_signature(step) + ((('u8',) if cargs.x_u8 else ())) + \
+                (((packing.LAYOUT_MODE[cargs.w_split],) if cargs.w_split else ()))
             if cargs.w_split:
                 ncfg = lib.dh_conv2d_num_halo_tile_cfgs() if cargs.w_split == 2 else lib.dh_conv2d_num_split_tile_cfgs()
             if step.kind == 'conv' and lib.dh_conv2d_uses_split_k(args[0]):

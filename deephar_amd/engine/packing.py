@@ -1,5 +1,6 @@
 """Host-side weight re-layout for the gfx950 kernels (delegates to the C-ABI so that other hosts get the
 exact same packing: dh_conv2d_pack_weights_host)."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -67,9 +68,22 @@ def unpack_conv(packed, kh, kw, cin, cout):
     return a[:k, :cout].reshape(kh, kw, cin, cout)
 
 
-SPLIT_PARTS = {1: 3, 3: 2, 4: 1}      # dh_conv_args.w_split of a split packing -> bf16 parts per operand
-WIDE_SPLIT_PARTS = {5: 3, 6: 2, 7: 1}  # the same for the extended scope's codes: the packings of 1 / 3 / 4 byte for byte
-WIDE_SPLIT_BASE = {5: 1, 6: 3, 7: 4}   # extended-scope code -> the standard code with the same packing
+Layout = collections.namedtuple('Layout', 'mode scope parts base')
+# THE vocabulary of dh_conv_args.w_split (include/deephar_hip.h): code -> the mode's name (Plan.gemm_precision; 'halo': the fp32
+# chunk-major packing of the halo-resident K x K kernel), the Plan.gemm_scope it is bound under (None: either), the bf16 parts
+# per operand (None: an fp32 packing) and the code whose packed bytes it shares.  Every other table is derived from this one.
+LAYOUTS = {
+    0: Layout('f32', None, None, 0),
+    2: Layout('halo', None, None, 2),
+    1: Layout('bf16x3', 'standard', 3, 1), 3: Layout('bf16x2', 'standard', 2, 3), 4: Layout('bf16', 'standard', 1, 4),
+    5: Layout('bf16x3', 'extended', 3, 1), 6: Layout('bf16x2', 'extended', 2, 3), 7: Layout('bf16', 'extended', 1, 4),
+}
+LAYOUT_MODE = {code: l.mode for code, l in LAYOUTS.items()}
+LAYOUT_CODES = {scope: {l.mode: code for code, l in LAYOUTS.items() if l.scope == scope} for scope in ('standard', 'extended')}
+MODE_PARTS = {l.mode: l.parts for l in LAYOUTS.values() if l.parts}              # gemm_precision -> bf16 parts per operand
+SPLIT_PARTS = {code: l.parts for code, l in LAYOUTS.items() if l.scope == 'standard'}
+WIDE_SPLIT_PARTS = {code: l.parts for code, l in LAYOUTS.items() if l.scope == 'extended'}    # the packings of 1 / 3 / 4
+WIDE_SPLIT_BASE = {code: l.base for code, l in LAYOUTS.items() if l.scope == 'extended'}      # ... byte for byte
 
 
 def pack_conv_split(w_hwio, parts=3):

@@ -86,7 +86,7 @@ def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=
         raise ValueError("split=True means precision='bf16x3', got precision=%r" % (precision,))
     if halo and precision not in (None, 'f32'):
         raise ValueError('the halo-resident kernel takes fp32 weights only')
-    w_split = {None: int(bool(split)), 'f32': 0, 'bf16x3': 1, 'bf16x2': 3, 'bf16': 4}[precision]
+    w_split = packing.LAYOUT_CODES['standard'].get(precision or ('bf16x3' if split else 'f32'), 0)
     if w_split and packed is None:
         pk, kp, np_ = packing.pack_conv_split(np.asarray(w_hwio, np.float32), parts=packing.SPLIT_PARTS[w_split])
         packed = (torch.from_numpy(pk).to(x.device), kp, np_)
@@ -100,7 +100,7 @@ def conv2d(x, w_hwio, strides=(1, 1), padding='same', pre_scale=None, pre_shift=
     if scope not in ('standard', 'extended'):
         raise ValueError("scope must be 'standard' or 'extended', got %r" % (scope,))
     if scope == 'extended' and w_split:
-        w_split = {1: 5, 3: 6, 4: 7}[w_split]
+        w_split = packing.LAYOUT_CODES['extended'][packing.LAYOUT_MODE[w_split]]
     a.w_split = 2 if halo else w_split
     a.x, a.w, a.y = _p(x), _p(wt), _p(y)
     a.pre_scale, a.pre_shift, a.post_scale, a.post_shift = _p(pre_scale), _p(pre_shift), _p(post_scale), _p(post_shift)
@@ -209,7 +209,7 @@ def conv2d_transpose(x, w, strides=(2, 2), pre_scale=None, pre_shift=None, pre_r
     been packed for the same mode (pack_convt_weight(..., parts=...))."""
     if precision not in (None, 'f32', 'bf16x3', 'bf16x2', 'bf16'):
         raise ValueError("precision must be 'f32', 'bf16x3', 'bf16x2' or 'bf16', got %r" % (precision,))
-    parts = {None: None, 'f32': None, 'bf16x3': 3, 'bf16x2': 2, 'bf16': 1}[precision]
+    parts = packing.MODE_PARTS.get(precision)
     torch = _t()
     kh, kw, cout, cin = w.shape
     if (kh, kw) != (2, 2) or tuple(strides) != (2, 2):

@@ -28,7 +28,6 @@ OPERANDS = ('x', 'y', 'res1', 'res2', 'y_pool')        # operand number k of sla
 NUM_GENERAL = 9                                        # tile_cfg 0..8: implicit-GEMM kernel; 9..17: the same tiles on the LDS-DMA GEMM
 TILES = ((2, 2, 2, 3), (2, 2, 2, 2), (4, 1, 1, 3), (4, 1, 1, 2), (4, 1, 1, 1), (2, 1, 1, 3), (2, 1, 1, 2), (2, 1, 1, 1),
          (1, 1, 1, 1))                                 # (WM, WN, TM, TN) of conv_igemm.hip: kCfgs / gemm1x1.hip: launch_gemm1x1
-SPLIT_PARTS = {1: 3, 3: 2, 4: 1}
 
 
 def same_pad(size, k, s):
@@ -345,7 +344,7 @@ def pack(case, w_hwio, device='cuda'):
     if case.w_split == 0:
         return F.pack_conv_weight(w_hwio, device)
     pk, kp, np_ = packing.pack_conv_halo(w_hwio) if case.w_split == 2 else \
-        packing.pack_conv_split(w_hwio, parts=SPLIT_PARTS[case.w_split])
+        packing.pack_conv_split(w_hwio, parts=packing.SPLIT_PARTS[case.w_split])
     return torch.from_numpy(pk).to(device), kp, np_
 
 

@@ -27,12 +27,13 @@ import bf16_modes_ref as B
 import paritylog
 import resample_ref as R
 from deephar_amd import graph as G
+from deephar_amd.engine.packing import LAYOUTS
 from oracle import ops
 
 SKIPPABLE = ('bn', 'relu', 'scale', 'sigmoid', 'add')      # shape-preserving nodes `skip=` can turn into the identity
 DECODER_OPS = ('expect2d', 'jointprob')      # the read-outs compare_decoder has a conditioned tolerance for
 LAYER_COST = dict(conv=1, sepconv=2, convtranspose=1)
-SPLIT_CODES = (1, 3, 4, 5, 6, 7)             # dh_conv_args.w_split of the split-bf16 packings (0: fp32, 2: the halo kernel's)
+SPLIT_CODES = tuple(sorted(c for c, l in LAYOUTS.items() if l.parts))      # dh_conv_args.w_split of the split-bf16 packings
 
 
 def _param(layer, role, dtype):

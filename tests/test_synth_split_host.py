@@ -2,7 +2,7 @@
 
 1. Classification.  For every graph of the split leg the default plan's conv / convtranspose steps are put to the LIBRARY's
    rules (dh_conv2d_split_eligible, dh_conv2d_split_wide_eligible, dh_conv2d_transpose2x2_split_eligible) with the launch
-   struct filled as Executor._bind fills it on a fake arena (`classify`).  tests/test_gpu_synth_graphs_split.py imports the
+   struct the engine's own binder fills (engine/binding.py) on its fake arena (`classify`).  tests/test_gpu_synth_graphs_split.py imports the
    table and holds the bound plan to it step by step.
 2. Coverage.  `COVERAGE` lists the (layer class, plan feature) pairs the split leg must meet on at least one (graph, shape).
 3. The twin.  The slice readers of slice_reader_odd are refused under every mode and scope, its sibling's are taken.
@@ -22,16 +22,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import graphref as GR                              # noqa: E402
 import synthgraphs as S                            # noqa: E402
 
+from deephar_amd.engine import binding            # noqa: E402
+from deephar_amd.engine.packing import LAYOUT_CODES as CODES, MODE_PARTS as PARTS    # noqa: E402
 from deephar_amd.engine.planner import build_plan  # noqa: E402
 from deephar_amd.engine.rules import RuleSet       # noqa: E402
 
 MODES = ('bf16x3', 'bf16x2', 'bf16')
-PARTS = {'bf16x3': 3, 'bf16x2': 2, 'bf16': 1}
-CODES = {'standard': {'bf16x3': 1, 'bf16x2': 3, 'bf16': 4}, 'extended': {'bf16x3': 5, 'bf16x2': 6, 'bf16': 7}}
 CONVT_CODES = CODES['standard']                    # (a transposed convolution has one rule and one set of codes)
 STD_PW, STD_KXK, EXT_KXK, EXT_BNPW, CONVT = 'standard pointwise', 'standard KxK', 'extended KxK', 'extended BN-pointwise', 'transposed'
 ADDED = (EXT_KXK, EXT_BNPW)                        # the classes only gemm_scope='extended' reaches
-FAKE_BASE = 256                                    # the arena's address: 16-byte aligned, as torch's allocations are
 
 
 def batch(H, W):
@@ -40,67 +39,6 @@ def batch(H, W):
 
 
 # ---- 1. classification -----------------------------------------------------------------------------------------------------
-def _ptr(v, n):
-    return FAKE_BASE + 4 * (v.buf.offset * n + v.coff)
-
-
-def conv_args(lib, s, n):
-    """dh_conv_args of a conv step as BoundPlan._bind fills it before it asks weight_layout (w / w_split left out)."""
-    from deephar_amd import _lib
-    a, x, y = s.attrs, s.ins['x'], s.outs['y']
-    args = _lib.ConvArgs()
-    args.x, args.y = _ptr(x, n), _ptr(y, n)
-    if 'pre_bn' in s.params:
-        args.pre_scale, args.pre_shift = 1 << 20, 2 << 20
-    if 'post_bn' in s.params or 'post_affine' in s.params:
-        args.post_scale, args.post_shift = 3 << 20, 4 << 20
-    up = 2 if a['up2'] else 1
-    args.N = n * x.lead(3)
-    args.H, args.W, args.Cin, args.ldx = x.shape[-3], x.shape[-2], x.C, x.ld
-    sg = a.get('seg')
-    if sg is not None:
-        args.H, args.W, args.Cin = x.shape[-3] // sg['pool_sh'], x.shape[-2] // 2, a['Cin']
-    rs = a.get('x_resample', 0)
-    if rs:
-        args.x_resample = rs
-        args.H, args.W = (2 * x.shape[-3], 2 * x.shape[-2]) if rs == 1 else (x.shape[-3] // 2, x.shape[-2] // 2)
-    args.OH, args.OW, args.Cout, args.ldy = y.shape[-3] // up, y.shape[-2] // up, a['Cout'], y.ld
-    args.KH, args.KW, args.SH, args.SW, args.PT, args.PL = a['kh'], a['kw'], a['sh'], a['sw'], a['pt'], a['pl']
-    kp, np_ = C.c_int(), C.c_int()
-    assert lib.dh_conv2d_packed_dims(a['kh'], a['kw'], args.Cin, a['Cout'], C.byref(kp), C.byref(np_)) == 0
-    args.K, args.Kp, args.Np = a['K'], kp.value, np_.value
-    r1, r2 = s.ins.get('res1'), s.ins.get('res2')
-    if r1 is not None:
-        args.res1, args.ldr1 = _ptr(r1, n), r1.ld
-    if r2 is not None:
-        args.res2, args.ldr2 = _ptr(r2, n), r2.ld
-    args.pre_relu, args.post_relu, args.up2 = a['pre_relu'], a['post_relu'], a['up2']
-    args.res2_down = a.get('res2_down', 0)
-    yp = s.outs.get('ypool')
-    if yp is not None:
-        args.y_pool, args.ldyp = _ptr(yp, n), yp.ld
-    return args
-
-
-def convt_args(lib, s, n):
-    """dh_conv_transpose of a convtranspose step, likewise"""
-    from deephar_amd import _lib
-    a, x, y = s.attrs, s.ins['x'], s.outs['y']
-    args = _lib.ConvtArgs()
-    args.x, args.y = _ptr(x, n), _ptr(y, n)
-    if 'pre_bn' in s.params:
-        args.pre_scale, args.pre_shift = 1 << 20, 2 << 20
-    r1 = s.ins.get('res1')
-    if r1 is not None:
-        args.res, args.ldr = _ptr(r1, n), r1.ld
-    args.N, args.H, args.W, args.Cin, args.ldx = n * x.lead(3), x.shape[-3], x.shape[-2], x.C, x.ld
-    kp, np_ = C.c_int(), C.c_int()
-    assert lib.dh_conv2d_packed_dims(1, 1, x.C, 4 * a['Cout'], C.byref(kp), C.byref(np_)) == 0
-    args.Cout, args.ldy, args.Kp, args.Np = a['Cout'], y.ld, kp.value, np_.value
-    args.pre_relu, args.post_relu = a['pre_relu'], a['post_relu']
-    return args
-
-
 def features(s):
     """what a split layer meets in its fused step (the names of COVERAGE)"""
     a, x, y = s.attrs, s.ins['x'], s.outs['y']
@@ -141,17 +79,17 @@ def features(s):
 def classify(lib, plan, n):
     """One row per step of `plan` bound for n frames: None for a step that is no convolution, else a dict with the library's
     answers (`std`, `wide`), the layer class (`cls`: None where the layer stays fp32 under both scopes) and its features."""
-    rows = []
+    rows, env = [], binding.FakeEnv(n)
     for s in plan.steps:
         if s.kind == 'conv':
-            args = conv_args(lib, s, n)
+            args = binding.bind(s, n, env)[1][0]
             std, wide = lib.dh_conv2d_split_eligible(C.byref(args)), lib.dh_conv2d_split_wide_eligible(C.byref(args))
             assert wide >= std
             pw = s.attrs['kh'] == 1 and s.attrs['kw'] == 1
             cls = (STD_PW if pw else STD_KXK) if std else ((EXT_BNPW if 'pre_bn' in s.params else EXT_KXK) if wide else None)
             assert cls != EXT_BNPW or pw
         elif s.kind == 'convtranspose':
-            std = wide = lib.dh_conv2d_transpose2x2_split_eligible(C.byref(convt_args(lib, s, n)))
+            std = wide = lib.dh_conv2d_transpose2x2_split_eligible(C.byref(binding.bind(s, n, env)[1][0]))
             cls = CONVT if std else None
         else:
             rows.append(None)
@@ -272,7 +210,7 @@ def test_the_misaligned_twin_is_refused(tables, hip_lib):
             for mode in MODES:
                 for scope in ('standard', 'extended'):
                     assert expected_code(o, mode, scope) is None
-            a = conv_args(hip_lib, o['step'], batch(*shape[:2]))
+            a = binding.bind(o['step'], batch(*shape[:2]), binding.FakeEnv(batch(*shape[:2])))[1][0]
             a.x += 8                                   # the twin's view, two channels on: nothing else changes
             assert hip_lib.dh_conv2d_split_eligible(C.byref(a)) == g['std']
             assert hip_lib.dh_conv2d_split_wide_eligible(C.byref(a)) == g['wide']

@@ -29,7 +29,7 @@ from deephar_amd import _lib, functional as F                       # noqa: E402
 from deephar_amd.engine import packing                              # noqa: E402
 from bench_resampling import UP, alternate, timed                   # noqa: E402
 
-MODES = {'bf16x3': (3, 1), 'bf16x2': (2, 3), 'bf16': (1, 4)}        # mode -> (parts, dh_conv_args.w_split)
+MODES = {m: (packing.MODE_PARTS[m], c) for m, c in packing.LAYOUT_CODES['standard'].items()}   # mode -> (parts, dh_conv_args.w_split)
 
 
 def bench_convt(lib, st, dev, n, cin, cout, side, reps, inner):
