@@ -53,6 +53,14 @@ import numpy as np
 from .. import graph as G
 from .rules import RuleSet
 
+# dh_softargmax2d_context_f32 (rule R5b) stages an H x W map, 16 channel lanes wide, and the two coordinate grids in LDS;
+# launch_softargmax2d_context (csrc/decoder.hip) refuses a slab above this many bytes
+SAM_CTX_MAX_SLAB = 128 * 1024
+
+
+def sam_ctx_slab_bytes(H, W):
+    return (H * W * 16 + W + H) * 4
+
 
 class Buf:
     def __init__(self, items, kind='act'):
@@ -1433,6 +1441,10 @@ class Planner:
         J = hs.C
         if hs.buf is not hc.buf or hs.ld != hc.ld or hc.coff != hs.coff + J or hc.C != J * nctx or J % 4 or hs.ld % 4 or \
                 hs.coff % 4 or hs.shape[:-1] != hc.shape[:-1]:
+            return None
+        # the fused kernel keeps a frame's maps, 16 channel lanes wide, and both grids in LDS and has no unstaged variant: the
+        # library refuses (DH_EUNSUPPORTED) a slab above 128 KiB, e.g. 48 x 48 maps; the two read-outs then stay apart
+        if sam_ctx_slab_bytes(hs.shape[-3], hs.shape[-2]) > SAM_CTX_MAX_SLAB:
             return None
         # the fused step is emitted HERE, after everything planned so far: nothing already emitted may read what the two
         # read-outs wrote (under another topological order a consumer of the joint confidences could sit in between)

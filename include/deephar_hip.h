@@ -392,7 +392,9 @@ int dh_softargmax2d_f32(const dh_sam_args* a, void* stream);
  *   y[f, j] = agg_alpha * xy_j + (1 - agg_alpha) * sum_k xy_jk * conf_jk / sum_k conf_jk      -> y [F, J, 2], pitch ldy
  * a->conf_raw (optional, pitch ldcr) receives the J joint confidences; a->C = J * (1 + nctx); the other outputs of
  * dh_sam_args must be NULL.  Needs J % 4 == 0, nctx <= 3, ldh % 4 == 0 and a 16-byte aligned `h` (DH_EUNSUPPORTED
- * otherwise: use dh_softargmax2d_f32 twice + dh_context_aggregation_f32). */
+ * otherwise: use dh_softargmax2d_f32 twice + dh_context_aggregation_f32).  The kernel stages a frame's maps, 16 channel
+ * lanes wide, and both grids in LDS and has no unstaged variant: (H * W * 16 + W + H) * 4 bytes above 128 KiB (45 x 45 and
+ * 40 x 48 maps fit, 44 x 48 and 40 x 52 do not) are DH_EUNSUPPORTED as well, nothing is launched. */
 int dh_softargmax2d_context_f32(const dh_sam_args* a, int J, int nctx, float agg_alpha, float* y, int ldy,
                                 void* stream);
 

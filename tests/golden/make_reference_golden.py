@@ -17,6 +17,9 @@ either as a shape mismatch here or as a numeric mismatch in tests/test_reference
          eval_penn_ar_pe_merge.py at T = 16 / 4 blocks / 256 px, SPNet-NTU at T = 32 / 256 px with fitted heads, and
          [r06] the model of the reference's own speed protocol, eval_speed2d.py:31-43: SPNet-Penn, 6 pyramids, actions
          on all six, pose_replica, T = 8 at 256 px, fitted heads)
+    python tests/golden/make_reference_golden.py --rect     ->  tests/golden/reference_models_rect.npz
+        (non-square frames: 2-block ReceptionNet 2-D with context at 192 x 256 and at 256 x 192, 3-D at 192 x 256, SPNet
+         T = 4 / two pyramids / pose_replica at 128 x 192 -- outputs only)
     ... --real --only=spnet2d_speed_s,spnet3d_32_s           (recompute just these cases of the file)
 """
 import importlib
@@ -123,6 +126,9 @@ SMOOTH_TAGS = ('spnet3d_s', 'spnet2d_s', 'spnet2dr_s')
 OUT_SMOOTH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'reference_models_smooth.npz')
 REAL_TAGS = ('rec2d_8', 'rec3d_8', 'merge2d_16', 'spnet3d_32_s', 'spnet2d_speed_s')
 OUT_REAL = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'reference_models_real.npz')
+RECT_TAGS = ('rec2d_rect', 'rec2d_rect_t', 'rec3d_rect', 'spnet2dr_rect')
+RECT_FRAMES = {'rec2d_rect': (192, 256), 'rec2d_rect_t': (256, 192), 'rec3d_rect': (192, 256), 'spnet2dr_rect': (128, 192)}
+OUT_RECT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'reference_models_rect.npz')
 
 
 def build_pair(R, tag):
@@ -143,6 +149,18 @@ def build_pair(R, tag):
         ref = R['models.reception'].build((256, 256, 3), 17, dim=3, **kw)
         prod = prec.build((256, 256, 3), 17, dim=3, **kw)
         return ref, prod, draw(tag, (2, 256, 256, 3))
+    if tag in ('rec2d_rect', 'rec2d_rect_t'):      # 'rec2d' on non-square frames, both orientations
+        kw = dict(num_context_per_joint=2, num_blocks=2, ksize=(5, 5), concat_pose_confidence=False)
+        shape = RECT_FRAMES[tag] + (3,)
+        ref = R['models.reception'].build(shape, 16, dim=2, **kw)
+        prod = prec.build(shape, 16, dim=2, **kw)
+        return ref, prod, draw(tag, (2,) + shape)
+    if tag == 'rec3d_rect':
+        kw = dict(num_blocks=2, depth_maps=16, ksize=(5, 5))
+        shape = RECT_FRAMES[tag] + (3,)
+        ref = R['models.reception'].build(shape, 17, dim=3, **kw)
+        prod = prec.build(shape, 17, dim=3, **kw)
+        return ref, prod, draw(tag, (2,) + shape)
     if tag == 'rec2d_8':    # configs[1] at its real depth (reception.py:277-312 loop indices 3 .. 8)
         kw = dict(num_context_per_joint=2, num_blocks=8, ksize=(5, 5), concat_pose_confidence=False)
         ref = R['models.reception'].build((256, 256, 3), 16, dim=2, **kw)
@@ -186,21 +204,24 @@ def build_pair(R, tag):
                                                 # configs[4]: T = 32 -> time_stride 2 (spnet.py:100), 256 px
                                                 'spnet3d_32': (32, 'pa17j3d', 60, 2, [1, 2], 192, 256, False),
                                                 # exp/pennaction/eval_speed2d.py:31-43: the model the reference times
-                                                'spnet2d_speed': (8, 'pa16j2d', 15, 6, [1, 2, 3, 4, 5, 6], 160, 256, True)}[
+                                                'spnet2d_speed': (8, 'pa16j2d', 15, 6, [1, 2, 3, 4, 5, 6], 160, 256, True),
+                                                # the SPNet of tests/test_gpu_rect_models.py on 128 x 192 frames
+                                                'spnet2dr_rect': (4, 'pa16j2d', 15, 2, [1, 2], 160, None, True)}[
         tag[:-2] if smooth else tag]
+    rows, cols = RECT_FRAMES.get(tag, (res, res))
     R['models.spnet'].__dict__.pop('act_cnt', None)       # the reference's process-global counter
-    rcfg = R['config'].ModelConfig((T, res, res, 3), getattr(putils, lay), num_actions=[nact], num_pyramids=pyr,
+    rcfg = R['config'].ModelConfig((T, rows, cols, 3), getattr(putils, lay), num_actions=[nact], num_pyramids=pyr,
                                    action_pyramids=apyr, num_levels=4, pose_replica=rep,
                                    num_pose_features=feats, num_visual_features=feats)
     ref = R['models.spnet'].build(rcfg)
-    pcfg = pconfig.ModelConfig((T, res, res, 3), getattr(putils, lay), num_actions=[nact], num_pyramids=pyr,
+    pcfg = pconfig.ModelConfig((T, rows, cols, 3), getattr(putils, lay), num_actions=[nact], num_pyramids=pyr,
                                action_pyramids=apyr, num_levels=4, pose_replica=rep, num_pose_features=feats,
                                num_visual_features=feats)
     prod = pspn.build(pcfg)
     if smooth:
         import refgolden
         return ref, prod, refgolden.smooth_input(tag, res)[0].astype(np.float64)
-    return ref, prod, draw(tag, (1, T, res, res, 3))
+    return ref, prod, draw(tag, (1, T, rows, cols, 3))
 
 
 def keras_file_layout(ref_model):
@@ -254,7 +275,7 @@ def check_weight_files(tag, ref_model, product_model):
           ('by name' if by_name else 'by order', 'n/a (by-name family)' if by_name else 'by order'))
 
 
-def main(smooth=False, real=False, only=None):
+def main(smooth=False, real=False, only=None, rect=False):
     """only: comma list of tags -- just these cases are recomputed, the other arrays of the output file are kept as they
     are (a full run reproduces them bit for bit; this keeps an added or refitted case to minutes)."""
     import json
@@ -263,8 +284,8 @@ def main(smooth=False, real=False, only=None):
     R = load_reference()
     g = {}
     layouts = {}
-    tags = REAL_TAGS if real else SMOOTH_TAGS if smooth else TAGS
-    out = OUT_REAL if real else OUT_SMOOTH if smooth else OUT
+    tags = RECT_TAGS if rect else REAL_TAGS if real else SMOOTH_TAGS if smooth else TAGS
+    out = OUT_RECT if rect else OUT_REAL if real else OUT_SMOOTH if smooth else OUT
     if only:
         assert smooth or real, '--only is for the outputs-only files (--smooth / --real)'
         assert all(t in tags for t in only), (only, tags)
@@ -293,7 +314,7 @@ def main(smooth=False, real=False, only=None):
                 g['%s/%s/%d' % (tag, k, i)] = a.astype(np.float64 if k == 'f64' else np.float32)
         g['%s/nout' % tag] = np.array(len(outs['f64']))
         print(tag, 'outputs', [a.shape for a in outs['f64']], 'weights set', n, '%.0f s' % (time.time() - t0), flush=True)
-    if not smooth and not real:
+    if not smooth and not real and not rect:
         with open(os.path.join(os.path.dirname(OUT), 'keras_layouts.json'), 'w') as fh:
             json.dump(layouts, fh, separators=(',', ':'))
     np.savez_compressed(out, **g)
@@ -302,4 +323,4 @@ def main(smooth=False, real=False, only=None):
 
 if __name__ == '__main__':
     only = next((a.split('=', 1)[1].split(',') for a in sys.argv if a.startswith('--only=')), None)
-    main(smooth='--smooth' in sys.argv, real='--real' in sys.argv, only=only)
+    main(smooth='--smooth' in sys.argv, real='--real' in sys.argv, only=only, rect='--rect' in sys.argv)

@@ -15,13 +15,19 @@ GOLDEN_SMOOTH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden
 # model exactly as exp/pennaction/eval_penn_ar_pe_merge.py:51-57 builds it: T = 16, 4 blocks, nine action heads;
 # SPNet-NTU at T = 32 / 256 px, where spnet.py:100 switches time_stride to 2) -- outputs only
 GOLDEN_REAL = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_models_real.npz')
+# the '<tag>_rect' cases: non-square frames, (rows, columns) in RECT_FRAMES -- 2-block ReceptionNet 2-D with context in both
+# orientations, 2-block ReceptionNet 3-D, and the SPNet of tests/test_gpu_rect_models.py (T = 4, two pyramids, actions on both,
+# pose_replica) on per-pixel-noise clips with un-calibrated heads (a stress case like 'spnet2dr') -- outputs only
+GOLDEN_RECT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_models_rect.npz')
+RECT_FRAMES = {'rec2d_rect': (192, 256), 'rec2d_rect_t': (256, 192), 'rec3d_rect': (192, 256), 'spnet2dr_rect': (128, 192)}
 SPNET_CASES = {'spnet3d': (4, 'pa17j3d', 60, 2, [1, 2], 192, False),
                'spnet2d': (16, 'pa16j2d', 15, 2, [2], 160, False),
                'spnet2dr': (8, 'pa16j2d', 15, 6, [5, 6], 160, True),
                'spnet3d_32': (32, 'pa17j3d', 60, 2, [1, 2], 192, False),
                # [r06] the model of the reference's speed protocol, exp/pennaction/eval_speed2d.py:31-43: six pyramids,
                # actions on ALL six, pose_replica=True, 8-frame clips at 256 px (18 pose + 18 action outputs)
-               'spnet2d_speed': (8, 'pa16j2d', 15, 6, [1, 2, 3, 4, 5, 6], 160, True)}
+               'spnet2d_speed': (8, 'pa16j2d', 15, 6, [1, 2, 3, 4, 5, 6], 160, True),
+               'spnet2dr_rect': (4, 'pa16j2d', 15, 2, [1, 2], 160, True)}
 SPNET_RES = {'spnet3d_32': 256, 'spnet2d_speed': 256}          # input resolution (default 128)
 # seed of the video clip / peak positions of a '<tag>_s' case (31 + the case's rank among the round-5 cases; fixed numbers
 # since round 6 so that a new case does not move the old ones)
@@ -59,7 +65,7 @@ def spnet_ocfg(tag):
 
 
 def golden_file(tag):
-    return GOLDEN_REAL if tag in REAL_CASES else GOLDEN_SMOOTH if tag.endswith('_s') else GOLDEN
+    return GOLDEN_RECT if tag in RECT_CASES else GOLDEN_REAL if tag in REAL_CASES else GOLDEN_SMOOTH if tag.endswith('_s') else GOLDEN
 
 
 def golden(tag):
@@ -85,6 +91,16 @@ def build_case(tag):
         kw = dict(num_blocks=2, depth_maps=16, ksize=(5, 5), export_heatmaps=True)
         m = reception.build((256, 256, 3), 17, dim=3, **kw)
         x = case_input(tag, (2, 256, 256, 3))
+        run = lambda wd, dt: oref.forward(wd, x, 17, 3, dtype=dt, **kw)
+    elif tag in ('rec2d_rect', 'rec2d_rect_t'):
+        kw = dict(num_context_per_joint=2, num_blocks=2, ksize=(5, 5), concat_pose_confidence=False)
+        m = reception.build(RECT_FRAMES[tag] + (3,), 16, dim=2, **kw)
+        x = case_input(tag, (2,) + RECT_FRAMES[tag] + (3,))
+        run = lambda wd, dt: oref.forward(wd, x, 16, 2, dtype=dt, **kw)
+    elif tag == 'rec3d_rect':
+        kw = dict(num_blocks=2, depth_maps=16, ksize=(5, 5))
+        m = reception.build(RECT_FRAMES[tag] + (3,), 17, dim=3, **kw)
+        x = case_input(tag, (2,) + RECT_FRAMES[tag] + (3,))
         run = lambda wd, dt: oref.forward(wd, x, 17, 3, dtype=dt, **kw)
     elif tag == 'rec2d_8':      # configs[1]: 8 blocks, 2 contexts per joint (exp/mpii/eval_mpii_singleperson.py:46-50)
         kw = dict(num_context_per_joint=2, num_blocks=8, ksize=(5, 5), concat_pose_confidence=False)
@@ -119,10 +135,11 @@ def build_case(tag):
         T, lay, nact, pyr, apyr, feats, rep = SPNET_CASES[tag[:-2] if tag.endswith('_s') else tag]
         layout = getattr(utils, lay)
         res = SPNET_RES.get(tag[:-2] if tag.endswith('_s') else tag, 128)
-        cfg = ModelConfig((T, res, res, 3), layout, num_actions=[nact], num_pyramids=pyr, action_pyramids=apyr,
+        rows, cols = RECT_FRAMES.get(tag, (res, res))
+        cfg = ModelConfig((T, rows, cols, 3), layout, num_actions=[nact], num_pyramids=pyr, action_pyramids=apyr,
                           num_levels=4, pose_replica=rep, num_pose_features=feats, num_visual_features=feats)
         m = spnet.build(cfg)
-        x = smooth_input(tag)[0] if tag.endswith('_s') else case_input(tag, (1, T, res, res, 3))
+        x = smooth_input(tag)[0] if tag.endswith('_s') else case_input(tag, (1, T, rows, cols, 3))
         ocfg = spnet_ocfg(tag)
         run = lambda wd, dt, taps=None: osp.forward(wd, x, ocfg, dtype=dt, taps=taps)
     else:
@@ -139,4 +156,5 @@ def build_case(tag):
 
 CASES = ['rec2d', 'rec3d', 'merge2d', 'merge3d', 'spnet3d', 'spnet2d', 'spnet2dr']
 SMOOTH_CASES = ['spnet3d_s', 'spnet2d_s', 'spnet2dr_s']
+RECT_CASES = ['rec2d_rect', 'rec2d_rect_t', 'rec3d_rect', 'spnet2dr_rect']
 REAL_CASES = ['rec2d_8', 'rec3d_8', 'merge2d_16', 'spnet3d_32_s', 'spnet2d_speed_s']

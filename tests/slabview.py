@@ -89,10 +89,12 @@ def same_bits(a, b):
 SAM_WIDE_BLOCKS = 1024             # `blocks16 >= 1024`: 16 channels per work-group once F * ceil(C / 16) fills the chip
 SAM_SLAB_WIDE = 128 * 1024         # bytes of LDS above which the 16-channel kernel reads the maps from memory
 SAM_SLAB_NARROW = 60 * 1024        # the same for the 4-channel kernel
-# the statements of the launcher the three numbers restate, as they stand in the source
+SAM_CTX_SLAB = 128 * 1024          # launch_softargmax2d_context: bytes of LDS (16 channel lanes) above which it REFUSES the launch
+# the statements of the launchers the four numbers restate, as they stand in the source
 SAM_SOURCE_LINES = ('const bool wide = blocks16 >= 1024;',
                     'constexpr size_t kMaxSlab = 128 * 1024;',
-                    'if (slab > (wide ? kMaxSlab : (size_t)60 * 1024)) {')
+                    'if (slab > (wide ? kMaxSlab : (size_t)60 * 1024)) {',
+                    'if (slab > 128 * 1024) return DH_EUNSUPPORTED;')
 
 
 def sam_slab_bytes(H, W, g):
@@ -113,4 +115,6 @@ SAM_VARIANT_SHAPES = {
     (1024, 46, 46, 3): (16, False),    # slab of 135 792 B
     (2, 64, 64, 5): (4, False),        # slab of 66 048 B
     (3, 16, 16, 17): (4, True),        # the shape of the view cases
+    (512, 6, 4, 17): (16, True),       # H != W, one orientation each (all four, both ways: tests/test_gpu_rect_ops.py)
+    (2, 48, 96, 5): (4, False),        # slab of 74 304 B
 }

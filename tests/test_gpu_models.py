@@ -22,11 +22,11 @@ from paritylog import PX_TOL, check as _check      # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def _build(dim, num_blocks, joints, **kw):
+def _build(dim, num_blocks, joints, input_shape=(256, 256, 3), **kw):
     from deephar_amd import graph, weights
     from deephar_amd.models import reception
     graph.reset_naming()
-    m = reception.build((256, 256, 3), joints, dim=dim, num_blocks=num_blocks, ksize=(5, 5), **kw)
+    m = reception.build(tuple(input_shape), joints, dim=dim, num_blocks=num_blocks, ksize=(5, 5), **kw)
     weights.init_synthetic(m, seed=0)
     return m, weights.as_dict(m)
 
@@ -549,15 +549,15 @@ def test_merge_action_model_parity(pose_dim, joints, version, hip_lib, cuda):
         np.testing.assert_allclose(hip[k].sum(-1), 1.0, rtol=1e-5)
 
 
-def _spnet(T, layout, num_actions, pyramids, action_pyramids, feats, replica=False, calibrate=None, res=256):
+def _spnet(T, layout, num_actions, pyramids, action_pyramids, feats, replica=False, calibrate=None, res=256, input_shape=None):
     """calibrate: frames [N, T, 256, 256, 3] -> heat-map heads are brought to logit std ~ 6 before the weights are
-    read out (paritylog.calibrate_spnet_heads)."""
+    read out (paritylog.calibrate_spnet_heads).  input_shape: (T, H, W, 3) of a non-square clip, in place of (T, res, res, 3)."""
     from deephar_amd import graph, weights, utils
     from deephar_amd.config import ModelConfig
     from deephar_amd.models import spnet
     graph.reset_naming()
     lay = getattr(utils, layout)
-    cfg = ModelConfig((T, res, res, 3), lay, num_actions=[num_actions], num_pyramids=pyramids,
+    cfg = ModelConfig(tuple(input_shape) if input_shape is not None else (T, res, res, 3), lay, num_actions=[num_actions], num_pyramids=pyramids,
                       action_pyramids=action_pyramids, num_levels=4, pose_replica=replica, num_pose_features=feats,
                       num_visual_features=feats)
     m = spnet.build(cfg)

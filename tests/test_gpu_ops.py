@@ -129,8 +129,9 @@ def test_pointwise_bn_prologue_on_the_dma_kernel(cin, cout, relu, hip_lib, cuda)
 
 
 @pytest.mark.parametrize('ks,cout,bn', [(3, 32, True), (7, 64, False), (7, 32, True), (3, 64, False)])
-def test_first_layer_kernel(ks, cout, bn, hip_lib, cuda):
-    """Round 4: conv_stem.hip -- 3 input channels, stride 2, TF-SAME asymmetric padding, 256 x 256 frames -> 128 x 128 maps
+def test_first_layer_kernel(ks, cout, bn, hip_lib, cuda, frame=(256, 256)):
+    """(`frame`: tests/test_gpu_rect_ops.py runs this body on 192 x 256 and 256 x 192 frames: the rule wants 128 output columns.)
+    Round 4: conv_stem.hip -- 3 input channels, stride 2, TF-SAME asymmetric padding, 256 x 256 frames -> 128 x 128 maps
     (reception.py:61-66: 3x3 3->32 + BN + ReLU; spnet.py:317-322: 7x7 3->64).  The library takes such a layer by a rule on
     its geometry (dh_conv2d_uses_first_layer_kernel), whatever tiling is asked for; checked vs the oracle (fp32 and fp64),
     raw uint8 frames = the loader's float32 values (bitwise), batch-size invariance (bitwise)."""
@@ -143,7 +144,8 @@ def test_first_layer_kernel(ks, cout, bn, hip_lib, cuda):
     qs, qb = rng.uniform(0.5, 1.5, cout).astype(np.float32), _rand(rng, (cout,), 0.3)
     d = lambda a: torch.from_numpy(a).to(cuda)
     kw = dict(post_scale=d(qs), post_shift=d(qb), post_relu=True) if bn else {}
-    xb = rng.integers(0, 256, (n, 256, 256, 3), dtype=np.uint8)
+    fh, fw = frame
+    xb = rng.integers(0, 256, (n, fh, fw, 3), dtype=np.uint8)
     lut = normalization_lut(3, 1)
     x = lut[np.arange(3)[None, None, None, :], xb]                             # the loader's float32 values
     t = lambda a: torch.from_numpy(a)
@@ -155,7 +157,7 @@ def test_first_layer_kernel(ks, cout, bn, hip_lib, cuda):
     forced = F.conv2d(d(x), k, (2, 2), 'same', tile_cfg=4, **kw)                # the rule overrides the tiling
     one = F.conv2d(d(x[1:2]), k, (2, 2), 'same', **kw)
     torch.cuda.synchronize()
-    assert got.shape == (n, 128, 128, cout)
+    assert got.shape == (n, fh // 2, fw // 2, cout)
     _close(got, ref, atol=3e-5, what='first layer %dx%d -> %d' % (ks, ks, cout))
     e_hip = (got.cpu().double() - ref64).abs().max().item()
     e_cpu = (ref.double() - ref64).abs().max().item()
@@ -164,21 +166,22 @@ def test_first_layer_kernel(ks, cout, bn, hip_lib, cuda):
     assert torch.equal(got, forced) and torch.equal(got[1:2], one)
     # the rule itself
     a = _lib.ConvArgs()
-    a.N, a.H, a.W, a.Cin, a.ldx, a.OH, a.OW, a.Cout, a.ldy = n, 256, 256, 3, 3, 128, 128, cout, cout
+    a.N, a.H, a.W, a.Cin, a.ldx, a.OH, a.OW, a.Cout, a.ldy = n, fh, fw, 3, 3, fh // 2, fw // 2, cout, cout
     a.KH, a.KW, a.SH, a.SW, a.PT, a.PL, a.K = ks, ks, 2, 2, (ks - 2) // 2, (ks - 2) // 2, ks * ks * 3
     a.x = a.w = a.y = 16
-    assert hip_lib.dh_conv2d_uses_first_layer_kernel(C.byref(a)) == 1
-    for field, val in (('OW', 64), ('Cin', 4), ('SH', 1), ('Cout', 48), ('w_split', 1), ('pre_relu', 1)):
+    assert hip_lib.dh_conv2d_uses_first_layer_kernel(C.byref(a)) == (1 if fw // 2 == 128 else 0)
+    for field, val in (('OW', 64), ('Cin', 4), ('SH', 1), ('Cout', 48), ('w_split', 1), ('pre_relu', 1)) if fw // 2 == 128 else ():
         b_ = _lib.ConvArgs.from_buffer_copy(a)
         setattr(b_, field, val)
         assert hip_lib.dh_conv2d_uses_first_layer_kernel(C.byref(b_)) == 0, field
 
 
-def test_conv2d_fused_prologue_epilogue(hip_lib, cuda):
-    """BN -> ReLU -> conv -> BN -> (+res1 +res2) -> ReLU in one launch vs the unfused oracle chain."""
+def test_conv2d_fused_prologue_epilogue(hip_lib, cuda, shape=(2, 16, 16, 64)):
+    """BN -> ReLU -> conv -> BN -> (+res1 +res2) -> ReLU in one launch vs the unfused oracle chain.
+    (`shape`: tests/test_gpu_rect_ops.py runs this body on 16 x 20 and 20 x 16 maps.)"""
     from deephar_amd import functional as F
     rng = np.random.default_rng(7)
-    n, h, w, cin, cout = 2, 16, 16, 64, 96
+    (n, h, w, cin), cout = shape, 96
     x = _rand(rng, (n, h, w, cin))
     k = _rand(rng, (3, 3, cin, cout), 0.06)
     ps, pb = rng.uniform(0.5, 1.5, cin).astype(np.float32), _rand(rng, (cin,), 0.3)
@@ -211,11 +214,12 @@ def test_conv2d_prologue_keeps_padding_zero(hip_lib, cuda):
 
 
 @pytest.mark.parametrize('cout,cfg', [(288, -1), (576, -1), (96, 5), (64, 1), (576, 11), (288, 13), (96, 9)])
-def test_conv2d_fused_upsample_add(cout, cfg, hip_lib, cuda):
-    """conv -> BN -> +res1 -> UpSampling2D -> +res2 (reception.py:122-127) in the conv epilogue."""
+def test_conv2d_fused_upsample_add(cout, cfg, hip_lib, cuda, shape=(2, 8, 8, 288)):
+    """conv -> BN -> +res1 -> UpSampling2D -> +res2 (reception.py:122-127) in the conv epilogue.
+    (`shape`: tests/test_gpu_rect_ops.py runs this body on 6 x 10 and 10 x 6 maps.)"""
     from deephar_amd import functional as F
     rng = np.random.default_rng(cout)
-    n, h, w, cin = 2, 8, 8, 288
+    n, h, w, cin = shape
     x, k = _rand(rng, (n, h, w, cin)), _rand(rng, (1, 1, cin, cout), 0.06)
     qs, qb = rng.uniform(0.5, 1.5, cout).astype(np.float32), _rand(rng, (cout,), 0.3)
     r1, r2 = _rand(rng, (n, h, w, cout)), _rand(rng, (n, 2 * h, 2 * w, cout))
@@ -282,6 +286,8 @@ def test_dwconv_reads_an_upsampled_input(shape, k, hip_lib, cuda):
     (16, 16, 16, 384, 288, 'plain', True),         # ... depthwise at 32 x 32: several bands
     (3, 8, 8, 96, 288, 'bn+res1', False),          # an epilogue on the conv side, ragged GEMM tiles (M = 192)
     (2, 16, 16, 64, 272, 'res1+res2', False),
+    (3, 8, 16, 96, 288, 'bn+res1', False),         # H != W, both orientations: the depthwise half's bands and column tiles
+    (3, 16, 8, 96, 288, 'bn+res1', False),
 ])
 def test_conv_dw_grouped_launch(case, hip_lib, cuda):
     """[r06] dh_conv2d_dw_group_f32: the 1x1 shortcut convolution and the depthwise convolution of a pre-activation residual
@@ -485,10 +491,12 @@ def test_pool_bit_exact(shape, pool, strides, pad, hip_lib, cuda):
         assert torch.equal(got, ref)
 
 
-def test_upsample_add_bit_exact(hip_lib, cuda):
+def test_upsample_add_bit_exact(hip_lib, cuda, shape=(2, 8, 8, 288)):
+    """(`shape` of the low-resolution operand: tests/test_gpu_rect_ops.py runs this body on 6 x 10 and 10 x 6 maps.)"""
     from deephar_amd import functional as F
     rng = np.random.default_rng(5)
-    a, b = _rand(rng, (2, 16, 16, 288)), _rand(rng, (2, 8, 8, 288))
+    n, h, w, c = shape
+    a, b = _rand(rng, (n, 2 * h, 2 * w, c)), _rand(rng, (n, h, w, c))
     ref = torch.from_numpy(a) + O.upsample2d(torch.from_numpy(b))
     got = F.upsample2x_add(torch.from_numpy(b).to(cuda), torch.from_numpy(a).to(cuda)).cpu()
     assert torch.equal(got, ref)
@@ -497,7 +505,8 @@ def test_upsample_add_bit_exact(hip_lib, cuda):
 
 @pytest.mark.parametrize('shape,alpha', [((4, 32, 32, 16), 1.0), ((3, 32, 32, 32), 1.0), ((2, 32, 32, 17), 1.0),
                                          ((2, 16, 16, 17), 2.5), ((3, 8, 8, 20), 1.0), ((2, 4, 4, 17), 0.7),
-                                         ((1, 32, 32, 272), 1.0)])
+                                         ((1, 32, 32, 272), 1.0),
+                                         ((3, 12, 20, 17), 1.0), ((3, 20, 12, 17), 2.5)])     # H != W, both orientations
 def test_softargmax2d(shape, alpha, hip_lib, cuda):
     """Coordinates within 1e-3 px of a 256-px crop (|d| <= 3.9e-6 in normalised units)."""
     from deephar_amd import functional as F
@@ -532,7 +541,8 @@ def test_softargmax2d_known_answers(hip_lib, cuda):
 
 
 @pytest.mark.parametrize('shape,joints,nctx', [((3, 32, 32, 48), 16, 2), ((2, 16, 16, 52), 12, 3), ((2, 32, 32, 8), 4, 1),
-                                               ((1, 8, 8, 64), 16, 2)])
+                                               ((1, 8, 8, 64), 16, 2),
+                                               ((2, 12, 16, 52), 12, 3), ((2, 16, 12, 52), 12, 3)])     # H != W
 def test_softargmax2d_with_context_in_one_launch(shape, joints, nctx, hip_lib, cuda):
     """dh_softargmax2d_context_f32 = the 2-D decoder with context of reception.pose_regression_2d_context in one launch:
     against the oracle's soft-argmax / keypoint confidence / context aggregation (1e-3 px on the pose) and against the
@@ -1101,7 +1111,8 @@ def test_conv2d_dma_gemm_tilings_bitwise(case, hip_lib, cuda):
 
 
 @pytest.mark.parametrize('case', [(64, 32, 32, 48, 576, True), (3, 32, 32, 64, 96, False), (2, 16, 16, 288, 288, True),
-                                  (1, 30, 30, 64, 100, False)])
+                                  (1, 30, 30, 64, 100, False),
+                                  (2, 16, 20, 64, 96, False), (2, 20, 16, 64, 96, True)])     # H != W, both orientations
 def test_three_way_add_every_tiling(case, hip_lib, cuda):
     """[r05] out = BN(conv(relu?(x))) + res1 + res2 with BOTH residuals at full resolution -- fReMap's re-injection,
     add([ident_map, x, h]) of reception.py:312 (an HBM-bound launch: K = 48, 97 us at 4.8 TB/s).  Same additions in the same

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from refgolden import CASES, REAL_CASES, SMOOTH_CASES, build_case, golden
+from refgolden import CASES, REAL_CASES, RECT_CASES, SMOOTH_CASES, build_case, golden
 
 
 @pytest.mark.parametrize('tag', CASES + SMOOTH_CASES)
@@ -39,6 +39,14 @@ def test_oracle_matches_reference_code_at_real_size(tag):
     assert [o.shape for o in o64] == [g.shape for g in g64]
     for k, (a, b) in enumerate(zip(o64, g64)):
         assert np.abs(a - b).max() <= 1e-9 * max(1.0, np.abs(b).max()), (tag, k, np.abs(a - b).max())
+
+
+@pytest.mark.parametrize('tag', RECT_CASES)
+def test_oracle_matches_reference_code_on_non_square_frames(tag):
+    """192 x 256 and 256 x 192 frames (ReceptionNet 2-D with context in both orientations, 3-D), 128 x 192 clips (SPNet): the
+    oracle's linspace_2d grids, window guards and reshapes keep rows and columns apart the way the reference's own model code
+    does -- fp64 to 1e-9, fp32 to 2e-5, as for the square cases."""
+    test_oracle_matches_reference_code(tag)
 
 
 # [r06] the two real-size SPNet goldens must be resolvable in plain fp32 with a factor of two to spare: the round-5 fit of

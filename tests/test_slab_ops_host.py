@@ -18,6 +18,11 @@ def test_softargmax2d_shapes_reach_all_four_instantiations():
     for line in SV.SAM_SOURCE_LINES:
         assert src.count(line) == 1, 'launch_softargmax2d no longer says `%s`: restate slabview.sam_variant' % line
     assert 'const size_t slab = ((size_t)a.H * a.W * g + a.W + a.H) * sizeof(float);' in src
+    # the fused read-out (rule R5b) has no unstaged variant: the planner restates its refusal (tests/test_rect_host.py)
+    from deephar_amd.engine import planner
+    assert 'const size_t slab = ((size_t)a.H * a.W * CG + a.W + a.H) * sizeof(float);' in src and 'constexpr int CG = 16;' in src
+    assert planner.SAM_CTX_MAX_SLAB == SV.SAM_CTX_SLAB
+    assert all(planner.sam_ctx_slab_bytes(h, w) == SV.sam_slab_bytes(h, w, 16) for h, w in ((45, 45), (40, 52), (3, 300)))
     for shape, want in SV.SAM_VARIANT_SHAPES.items():
         assert SV.sam_variant(*shape) == want, (shape, SV.sam_variant(*shape), want)
     assert set(SV.SAM_VARIANT_SHAPES.values()) == {(16, True), (16, False), (4, True), (4, False)}
