@@ -59,6 +59,33 @@ class SamArgs(C.Structure):
                [('alpha', C.c_float), ('conf_scale', C.c_float), ('xy_times_conf', i32)]
 
 
+class ConvRoute(C.Structure):                    # == struct dh_conv_route: what dh_conv2d_f32 will do (dh_conv2d_route)
+    _fields_ = [(n, i32) for n in ('rc', 'kernel', 'tile_cfg', 'parts', 'bm', 'bn', 'tm', 'vec4', 'epi', 'pool')] + \
+               [('tiles', C.c_uint32)]
+
+
+class SamRoute(C.Structure):                     # == struct dh_sam_route (dh_softargmax2d_route)
+    _fields_ = [(n, i32) for n in ('rc', 'channels', 'staged', 'ctx_rc')]
+
+
+# dh_conv_route.kernel
+CONV_GENERAL, CONV_DMA, CONV_SPLIT, CONV_SPLIT_EXT, CONV_HALO, CONV_SKINNY, CONV_FIRST_LAYER = range(1, 8)
+
+
+def conv_route(lib, args, tile_cfg=-1):
+    """dh_conv2d_route as a ConvRoute."""
+    r = ConvRoute()
+    assert lib.dh_conv2d_route(C.byref(args), tile_cfg, C.byref(r)) == 0
+    return r
+
+
+def sam_route(lib, args, J=0, nctx=0):
+    """dh_softargmax2d_route as a SamRoute."""
+    r = SamRoute()
+    assert lib.dh_softargmax2d_route(C.byref(args), J, nctx, C.byref(r)) == 0
+    return r
+
+
 # name -> (restype, argtypes); every symbol include/deephar_hip.h declares
 SIGNATURES = {
     'dh_version': (C.c_int, []),
@@ -77,6 +104,7 @@ SIGNATURES = {
     'dh_conv2d_split_wide_eligible': (C.c_int, [C.POINTER(ConvArgs)]),
     'dh_conv2d_halo_eligible': (C.c_int, [C.POINTER(ConvArgs)]),
     'dh_conv2d_num_halo_tile_cfgs': (C.c_int, []),
+    'dh_conv2d_route': (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.POINTER(ConvRoute)]),
     'dh_conv2d_f32': (C.c_int, [C.POINTER(ConvArgs), C.c_int, vp]),
     'dh_normalize_u8_f32': (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp]),
     'dh_dwconv2d_f32': (C.c_int, [C.POINTER(DwArgs), vp]),
@@ -94,6 +122,7 @@ SIGNATURES = {
     'dh_eltwise_f32': (C.c_int, [C.POINTER(EltArgs), vp]),
     'dh_softargmax2d_f32': (C.c_int, [C.POINTER(SamArgs), vp]),
     'dh_softargmax2d_context_f32': (C.c_int, [C.POINTER(SamArgs), C.c_int, C.c_int, C.c_float, vp, C.c_int, vp]),
+    'dh_softargmax2d_route': (C.c_int, [C.POINTER(SamArgs), C.c_int, C.c_int, C.POINTER(SamRoute)]),
     'dh_context_aggregation_f32': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp]),
     'dh_depth_means_f32': (C.c_int, [vp, C.c_int, vp, vp] + [C.c_int] * 4 + [vp]),
     'dh_softargmax1d_f32': (C.c_int, [vp, vp, vp, C.c_int, vp] + [C.c_int] * 3 + [vp]),

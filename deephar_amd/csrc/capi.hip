@@ -16,6 +16,8 @@ static_assert(sizeof(dh_conv_args) == 200 && offsetof(dh_conv_args, y_pool) == 1
 static_assert(sizeof(dh_dw_args) == 88 && offsetof(dh_dw_args, up_in) == 84, "dh_dw_args layout");
 static_assert(sizeof(dh_dw_strided) == 104 && sizeof(dh_conv_transpose) == 96, "dh_dw_strided / dh_conv_transpose layout");
 static_assert(sizeof(dh_sam_args) == 112 && offsetof(dh_sam_args, xy_times_conf) == 108, "dh_sam_args layout");
+static_assert(sizeof(dh_conv_route) == 44 && offsetof(dh_conv_route, tiles) == 40, "dh_conv_route layout");
+static_assert(sizeof(dh_sam_route) == 16, "dh_sam_route layout");
 static inline int rc_of(hipError_t e) { return e == hipSuccess ? DH_OK : DH_ELAUNCH; }
 
 extern "C" {
@@ -103,8 +105,8 @@ int dh_conv2d_pack_weights_split_host(const float* w, uint16_t* packed, int KH, 
   return dh_conv2d_pack_weights_parts_host(w, packed, KH, KW, Cin, Cout, 3);
 }
 
-int dh_conv2d_num_tile_cfgs(void) { return conv_igemm_num_cfgs(); }
-int dh_conv2d_num_split_tile_cfgs(void) { return gemm1x1_split_num_cfgs(); }
+int dh_conv2d_num_tile_cfgs(void) { return kNumConvCfgs; }
+int dh_conv2d_num_split_tile_cfgs(void) { return kNumSplitCfgs; }
 int dh_conv2d_uses_split_k(const dh_conv_args* a) { return a != nullptr && conv_is_skinny(*a) ? 1 : 0; }
 int dh_conv2d_uses_first_layer_kernel(const dh_conv_args* a) {
   return a != nullptr && !conv_is_skinny(*a) && conv_stem_eligible(*a) ? 1 : 0;
@@ -113,14 +115,23 @@ int dh_conv2d_pick_tile_cfg(int M, int Cout) { return conv_igemm_pick_cfg(M, Cou
 int dh_conv2d_split_eligible(const dh_conv_args* a) { return a != nullptr && gemm1x1_split_eligible(*a) ? 1 : 0; }
 int dh_conv2d_split_wide_eligible(const dh_conv_args* a) { return a != nullptr && gemm1x1_split_wide_eligible(*a) ? 1 : 0; }
 int dh_conv2d_halo_eligible(const dh_conv_args* a) { return a != nullptr && conv_halo_eligible(*a) ? 1 : 0; }
-int dh_conv2d_num_halo_tile_cfgs(void) { return conv_halo_num_cfgs(); }
+int dh_conv2d_num_halo_tile_cfgs(void) { return kNumHaloCfgs; }
+
+// what dh_conv2d_f32 checks before it routes
+static int check_conv_args(const dh_conv_args* a) {
+  if (conv_check_pointers(a) != DH_OK) return DH_EINVAL;
+  if (a->res2_down && (a->res2 == nullptr || a->up2 || (a->OH & 1) || (a->OW & 1))) return DH_EINVAL;
+  return DH_OK;
+}
+
+int dh_conv2d_route(const dh_conv_args* a, int tile_cfg, dh_conv_route* out) {
+  if (a == nullptr || out == nullptr) return DH_EINVAL;
+  *out = check_conv_args(a) != DH_OK ? conv_refuse(DH_EINVAL) : conv_route(*a, tile_cfg);
+  return DH_OK;
+}
 
 int dh_conv2d_f32(const dh_conv_args* a, int tile_cfg, void* stream) {
-  if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
-  if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;
-  if ((a->post_scale == nullptr) != (a->post_shift == nullptr)) return DH_EINVAL;
-  if (a->SH <= 0 || a->SW <= 0 || a->KH <= 0 || a->KW <= 0) return DH_EINVAL;
-  if (a->res2_down && (a->res2 == nullptr || a->up2 || (a->OH & 1) || (a->OW & 1))) return DH_EINVAL;
+  if (check_conv_args(a) != DH_OK) return DH_EINVAL;
   return launch_conv_igemm(*a, tile_cfg, S(stream));
 }
 
@@ -134,15 +145,9 @@ int dh_conv2d_dw_group_f32(const dh_conv_args* a, const dh_dw_args* d, void* str
   return launch_conv_dw_group(*a, *d, S(stream));
 }
 
-// the argument checks dh_conv2d_f32 and launch_conv_igemm make, for the entry points that go to the skinny-conv kernel directly
+// the argument checks dh_conv2d_f32 and its route make, for the entry points that go to the skinny-conv kernel directly
 static int check_skinny_args(const dh_conv_args* c) {
-  if (c == nullptr || c->x == nullptr || c->w == nullptr || c->y == nullptr) return DH_EINVAL;
-  if ((c->pre_scale == nullptr) != (c->pre_shift == nullptr) || (c->post_scale == nullptr) != (c->post_shift == nullptr)) return DH_EINVAL;
-  if (c->SH <= 0 || c->SW <= 0 || c->KH <= 0 || c->KW <= 0 || c->N <= 0 || c->Cin <= 0 || c->Cout <= 0 || c->OH <= 0 || c->OW <= 0)
-    return DH_EINVAL;
-  if (c->Kp % 32 != 0 || c->Np % 32 != 0 || c->Kp < c->K || c->Np < c->Cout || c->K != c->KH * c->KW * c->Cin) return DH_EINVAL;
-  if ((long long)c->N * c->H * c->W > 0x7fffffffLL || (long long)c->N * c->OH * c->OW * (c->up2 ? 4 : 1) > 0x7fffffffLL) return DH_EINVAL;
-  return DH_OK;
+  return conv_check_pointers(c) != DH_OK || conv_check_geometry(*c) != DH_OK ? DH_EINVAL : DH_OK;
 }
 
 int dh_conv2d_pair_f32(const dh_conv_args* a, const dh_conv_args* b, void* stream) {
@@ -230,6 +235,12 @@ int dh_eltwise_f32(const dh_elt_args* a, void* stream) {
   if (a == nullptr) return DH_EINVAL;
   if ((a->scale == nullptr) != (a->shift == nullptr)) return DH_EINVAL;
   return launch_eltwise(*a, S(stream));
+}
+
+int dh_softargmax2d_route(const dh_sam_args* a, int J, int nctx, dh_sam_route* out) {
+  if (a == nullptr || out == nullptr) return DH_EINVAL;
+  *out = sam_route(*a, J, nctx);
+  return DH_OK;
 }
 
 int dh_softargmax2d_f32(const dh_sam_args* a, void* stream) {

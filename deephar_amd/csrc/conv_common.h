@@ -10,8 +10,6 @@ namespace dh {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-constexpr int kMaxPreKp = 4096;    // BN prologue of the LDS-DMA GEMMs: scale + shift tables of at most 2 x 16 KB in LDS
-
 // Epilogue traffic is streamed once (residual tiles in, output tile out), so it goes through non-temporal
 // accesses: it does not allocate in the caches and the operand tiles that other work-groups are about to re-read
 // stay resident.  Measured on the 65536 x 576 x 576 GEMM: 4-7 % faster (382 -> 356..368 us), thin GEMMs up to 11 %.
@@ -43,31 +41,6 @@ __device__ __forceinline__ void buf_st1_stream(RSRC rs, int voff, int soff, floa
 }
 __device__ __forceinline__ float& f4c(float4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 __device__ __forceinline__ float f4c(const float4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
-
-// Launch-side half of the direct epilogue: `epi` (1 = 16-byte epilogue possible) gains bit 1 when interior tiles may
-// store straight from the accumulators -- no up-sampling, no pooled second output, a second residual only at half
-// resolution, and every byte offset of y / res1 / res2 inside 31 bits (buffer offsets are 32-bit).
-inline int epi_with_direct(const ConvArgs& a, int epi, bool half_res_residual = true) {
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const int ohw = a.OH * a.OW;
-  // a second residual only in its half-resolution form, on maps where a wave's 32 pixels sit in one frame, start at an
-  // even image row and split into shifts: 2^a x 2^b >= 32 pixels, at least 8 wide
-  const bool r2ok = a.res2 == nullptr || (half_res_residual && a.res2_down && (a.OW & (a.OW - 1)) == 0 && (ohw & (ohw - 1)) == 0 && a.OW >= 8 &&
-                                          ohw >= 32 && (M / 4) * a.ldr2 * 4 < 0x7fffffffLL);
-  const bool direct = epi && !a.up2 && a.y_pool == nullptr && r2ok && M * a.ldy * 4 < 0x7fffffffLL &&
-                      (a.res1 == nullptr || M * a.ldr1 * 4 < 0x7fffffffLL);
-  return epi | (direct ? 2 : 0);
-}
-
-// Work-groups of a BM x BN tiling of the GEMM [M = N * OH * OW] x [Cout]: the grid's x dimension, so DH_EINVAL outside (0, 2^31)
-template <int BM, int BN>
-inline int gemm_tile_count(const ConvArgs& a, unsigned* tiles) {
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long t = ((M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-  if (t <= 0 || t > 0x7fffffffLL) return DH_EINVAL;
-  *tiles = (unsigned)t;
-  return DH_OK;
-}
 
 // XCD-aware bijective remap: block b runs on XCD b%8; give each XCD a contiguous run of tiles so the
 // workgroups that share one activation tile (consecutive N-tiles) hit the same L2.
@@ -154,20 +127,6 @@ struct EpiPrefetch {
   }
 };
 
-// Tilings whose epilogue can also write the 2x2 max-pooled output (dh_conv_args.y_pool): every wave owns ONE 32-row
-// block = one image row at OW == 32, and the waves come in (even, odd) pairs over M.
-template <int WM, int TM, bool UP2>
-constexpr bool conv_epilogue_pools() { return TM == 1 && WM % 2 == 0 && !UP2; }
-// [r06] OW == 16 / OW == 8: a wave's 32-row block is two / four WHOLE image rows (OH * OW a multiple of 32, so a block
-// never straddles frames and starts at an even row) -- the wave pools its own slab, no partner needed: any TM == 1 tiling.
-template <int TM, bool UP2>
-constexpr bool conv_epilogue_pools_in_wave() { return TM == 1 && !UP2; }
-// launch-side: may this tiling serve a.y_pool?
-template <int WM, int TM, bool UP2>
-inline bool conv_epilogue_pools_for(const ConvArgs& a) {
-  return a.OW == 32 ? conv_epilogue_pools<WM, TM, UP2>() : conv_epilogue_pools_in_wave<TM, UP2>();
-}
-
 struct EpiNoHook {
   __device__ __forceinline__ void operator()() const {}
 };
@@ -192,8 +151,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
   constexpr int IT = 4 * TN;
   constexpr int NSC = (64 % ROW4 == 0) ? 1 : 3;   // distinct column groups a lane meets over the row loop
   constexpr bool kPre = PRE && EpiPrefetch<TM, TN>::kEnabled;
-  constexpr bool kPool = conv_epilogue_pools<WM, TM, UP2>();
-  constexpr bool kPoolWave = conv_epilogue_pools_in_wave<TM, UP2>();
+  constexpr bool kPool = tile_pools_in_pairs(WM, TM, UP2);           // (gemm_family.h: the route asks the same functions)
+  constexpr bool kPoolWave = tile_pools_in_wave(TM, UP2);
   if constexpr (!UP2 && kPre && std::is_same<HOOK, EpiNoHook>::value) {
     if (EpiPrefetch<TM, TN>::template direct_tile<WM, WN>(p, m0, n0, M, epi_vec)) {
       // Direct path (interior tiles of plain launches): no LDS staging, no work-group barrier, no wait between the last

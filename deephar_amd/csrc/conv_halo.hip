@@ -27,11 +27,6 @@
 namespace dh {
 namespace {
 
-constexpr int HCH = 16;                   // channels per resident chunk
-constexpr int HPIX = 80;                  // LDS bytes per halo pixel (64 + 16 pad)
-constexpr int HMAXA = 12;                 // halo DMA instructions per wave (<= 48 KB per chunk)
-constexpr int HMAXB = 8;                  // weight-stage DMA passes (KW * BN <= 512)
-
 template <int... Is, typename F>
 __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
   (f(std::integral_constant<int, Is>{}), ...);
@@ -41,15 +36,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
-struct HaloGeom {
-  int ct_log2;      // output columns per tile = 1 << ct_log2 (OW, or 128 for wider rows)
-  int hr, hc;       // halo rows / columns
-  int a_bytes;      // one halo buffer, rounded up to whole 1 KB DMA instructions
-  int nbuf_a;       // 1 or 2 halo buffers
-  int b_bytes;      // one weight stage, rounded up to whole 4 KB DMA passes
-  int bpass;
-  int hc_magic;     // (1 << 20) / hc + 1: px / hc for px < 1024 as one multiply and a shift (an integer divide is ~40 VALU)
-};
+struct HaloGeom : HaloTile {};           // (conv_rules.h: conv_halo_tile fills it, the route asks the same function)
 
 template <int KW, int TN, bool RELU>
 __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const ConvArgs p, const int epi_vec, const HaloGeom g) {
@@ -212,41 +199,11 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const ConvArgs p, con
   conv_epilogue<4, 1, 1, TN, false, true, EpiNoHook, false>(p, acc, smem, m0, n0, M, epi_vec, pre);
 }
 
-bool geometry(const ConvArgs& a, int tn, HaloGeom* g) {
-  const int bn = tn * 32;
-  int ct;
-  if (a.OW >= 128) {
-    if (a.OW % 128) return false;
-    ct = 128;
-  } else {
-    ct = a.OW;
-    if (ct < 8 || (ct & (ct - 1)) || (a.OH * a.OW) % 128) return false;
-  }
-  int lg = 0;
-  while ((1 << lg) < ct) ++lg;
-  const int rt = 128 / ct;
-  g->ct_log2 = lg;
-  g->hr = (rt - 1) * a.SH + a.KH;
-  g->hc = (ct - 1) * a.SW + a.KW;
-  g->a_bytes = (g->hr * g->hc * HPIX + 1023) & ~1023;
-  g->b_bytes = (4 * a.KW * bn * 16 + 4095) & ~4095;
-  g->bpass = g->b_bytes >> 12;
-  g->hc_magic = (1 << 20) / g->hc + 1;
-  if ((g->a_bytes >> 10) > 4 * HMAXA || g->bpass > HMAXB) return false;
-  // two work-groups per CU need <= 80 KB each; a second halo buffer (prefetch of the next chunk) when it fits
-  const int epi = 4 * 32 * (bn + 4) * 4;
-  const int one = g->a_bytes + 2 * g->b_bytes, two = 2 * g->a_bytes + 2 * g->b_bytes;
-  g->nbuf_a = (two <= 80 * 1024 && a.Cin > HCH) ? 2 : 1;
-  const int total = g->nbuf_a == 2 ? two : one;
-  return (total > epi ? total : epi) <= 80 * 1024;
-}
-
 template <int KW, int TN>
-int launch_tn(const ConvArgs& a, int epi, const HaloGeom& g, hipStream_t s) {
+int launch_tn(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
   constexpr int BN = TN * 32;
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long tiles = (M / 128) * ((a.Cout + BN - 1) / BN);
-  if (tiles <= 0 || tiles > 0x7fffffffLL) return DH_EINVAL;
+  HaloGeom g;
+  conv_halo_tile(a, TN, &g);
   const int epi_bytes = 4 * 32 * (BN + 4) * 4;
   int lds = g.nbuf_a * g.a_bytes + 2 * g.b_bytes;
   if (lds < epi_bytes) lds = epi_bytes;
@@ -256,64 +213,28 @@ int launch_tn(const ConvArgs& a, int epi, const HaloGeom& g, hipStream_t s) {
     lim_t.raise((const void*)conv_halo_kernel<KW, TN, true>, 80 * 1024);
     lim_f.raise((const void*)conv_halo_kernel<KW, TN, false>, 80 * 1024);
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), (size_t)lds, s, a, epi, g);
+  hipLaunchKernelGGL(kern, dim3(r.tiles), dim3(256), (size_t)lds, s, a, r.epi, g);
   return check_launch();
 }
 
 template <int KW>
-int launch_kw(const ConvArgs& a, int tn, int epi, const HaloGeom& g, hipStream_t s) {
-  switch (tn) {
-    case 1: return launch_tn<KW, 1>(a, epi, g, s);
-    case 2: return launch_tn<KW, 2>(a, epi, g, s);
-    case 3: return launch_tn<KW, 3>(a, epi, g, s);
+int launch_kw(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  switch (r.tile_cfg) {
+    case 0: return launch_tn<KW, 1>(a, r, s);
+    case 1: return launch_tn<KW, 2>(a, r, s);
+    case 2: return launch_tn<KW, 3>(a, r, s);
   }
   return DH_EINVAL;
 }
 
 }  // namespace
 
-// What the kernel can run: dense K x K with K > 1 somewhere, stride 1 (stride 2 keeps the tap-major kernels: its halo is
-// 4x the output tile), Cin a multiple of 16, float input, 16-byte aligned views, no BN prologue / fused up-sampling,
-// whole-row output tiles of 128 pixels, LDS budget.
-bool conv_halo_supported(const ConvArgs& a0) {
-  ConvArgs a = a0;
-  a.w_split = 0;
-  if (a.x_u8 || a.up2 || a.pre_scale != nullptr || conv_is_skinny(a)) return false;
-  if (a.KH * a.KW <= 1 || a.KH > 7 || !(a.KW == 1 || a.KW == 3 || a.KW == 5)) return false;
-  if (a.SH != 1 || a.SW != 1 || a.PT < 0 || a.PL < 0) return false;
-  if (a.Cin % HCH || a.Cin < 32 || a.ldx % 4 || !al16(a.x)) return false;
-  if ((long long)a.N * a.H * a.W * a.ldx * 4 > kMaxBufferBytes) return false;
-  if (a.OH * a.OW < 1024) return false;      // small maps keep the tap-major kernels (a per-frame rule: never on N)
-  HaloGeom g;
-  return geometry(a, 1, &g);
-}
-
-// The layers a binding gives to this kernel (dh_conv2d_halo_eligible; a rule on the per-frame geometry only): what it can
-// run AND what the LDS-DMA tap-major kernel cannot -- Cin not a multiple of 32 (SPNet's 48- and 144-channel 3x3 convs,
-// which otherwise fall to the register-gather kernel: 1.17-1.21x faster here).  With Cin % 32 == 0 the two kernels are
-// within +-5 % of each other (tools/bench_halo.py, profiles/r03_bench_halo.json), so those layers keep the tap-major
-// family and its tiling freedom.
-bool conv_halo_eligible(const ConvArgs& a) { return a.Cin % 32 != 0 && conv_halo_supported(a); }
-
-int conv_halo_num_cfgs() { return 3; }
-
-// cfg: 0, 1, 2 -> TN = 1, 2, 3 (output-channel tile 32, 64, 96); < 0: the widest that fits and divides the work well
-int launch_conv_halo(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  if (!conv_halo_supported(a) || !al16(a.w)) return DH_EUNSUPPORTED;
-  if (a.Kp % 32 || a.K != a.KH * a.KW * a.Cin) return DH_EINVAL;
-  if (cfg >= 3) return DH_EINVAL;
-  int tn = cfg + 1;
-  HaloGeom g;
-  if (cfg < 0) {
-    const int np = (a.Cout + 31) / 32;
-    tn = np % 3 == 0 ? 3 : (np % 2 == 0 ? 2 : (np >= 3 ? 3 : np));
-    while (tn > 1 && !geometry(a, tn, &g)) --tn;
-  }
-  if (!geometry(a, tn, &g)) return DH_EUNSUPPORTED;
+// The rule (conv_halo_supported / conv_halo_eligible) and the choice of TN are the route's (conv_rules.h, conv_route.h)
+int launch_conv_halo(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
   switch (a.KW) {
-    case 1: return launch_kw<1>(a, tn, epi, g, s);
-    case 3: return launch_kw<3>(a, tn, epi, g, s);
-    case 5: return launch_kw<5>(a, tn, epi, g, s);
+    case 1: return launch_kw<1>(a, r, s);
+    case 3: return launch_kw<3>(a, r, s);
+    case 5: return launch_kw<5>(a, r, s);
   }
   return DH_EUNSUPPORTED;
 }

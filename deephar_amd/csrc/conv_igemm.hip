@@ -21,7 +21,6 @@ namespace dh {
 
 namespace {
 
-constexpr int BK = 32;
 constexpr int LDA = BK + 4;  // floats; 144 B rows keep ds_read_b128 conflict-free (odd multiple of 16 B)
 
 template <int WM, int WN, int TM, int TN, bool VEC4, bool UP2>
@@ -236,145 +235,45 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_igemm_kernel(const ConvAr
   conv_epilogue<WM, WN, TM, TN, UP2, false>(p, acc, smem, m0, n0, M, epi_vec, pre);
 }
 
-struct Cfg { int wm, wn, tm, tn; };
-constexpr Cfg kCfgs[] = {
-    {2, 2, 2, 3},  // 0: 128 x 192
-    {2, 2, 2, 2},  // 1: 128 x 128
-    {4, 1, 1, 3},  // 2: 128 x  96
-    {4, 1, 1, 2},  // 3: 128 x  64
-    {4, 1, 1, 1},  // 4: 128 x  32
-    {2, 1, 1, 3},  // 5:  64 x  96
-    {2, 1, 1, 2},  // 6:  64 x  64
-    {2, 1, 1, 1},  // 7:  64 x  32
-    {1, 1, 1, 1},  // 8:  32 x  32
-};
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
+// every tiling of kGemmTiles[0..8] in three forms: float4 gather + fused up-sampling (where the tiling has it), float4, scalar
 template <int WM, int WN, int TM, int TN>
-int launch_cfg(const ConvArgs& a, bool vec4, int epi, hipStream_t s) {
+int launch_cfg(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-  unsigned tiles;
-  if (gemm_tile_count<BM, BN>(a, &tiles) != DH_OK) return DH_EINVAL;
-  constexpr int kStage = BM * LDA + BK * BN, kEpi = WM * WN * 32 * (TN * 32 + 4);
+  constexpr int kStage = BM * LDA + BK * BN, kEpi = gemm_epi_floats(WM, WN, TN);
   const size_t lds = (size_t)(kStage > kEpi ? kStage : kEpi) * sizeof(float);
-  if (a.y_pool != nullptr && !conv_epilogue_pools_for<WM, TM, false>(a)) return DH_EUNSUPPORTED;
-  if (a.up2) {
-    if (!vec4) return DH_EUNSUPPORTED;
-    if constexpr (TM * TN >= 6) return DH_EUNSUPPORTED;  // would spill; the dispatcher never asks for it
-    else
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, true>), dim3(tiles), dim3(NT), lds, s, a, epi);
-  } else if (vec4) {
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false>), dim3(tiles), dim3(NT), lds, s, a, epi);
+  if constexpr (tile_has_up2(GemmTile{WM, WN, TM, TN})) {
+    if (a.up2) {
+      hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, true>), dim3(r.tiles), dim3(NT), lds, s, a, r.epi);
+      return check_launch();
+    }
+  }
+  if (r.vec4) {
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, true, false>), dim3(r.tiles), dim3(NT), lds, s, a, r.epi);
   } else {
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false>), dim3(tiles), dim3(NT), lds, s, a, epi);
+    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, TM, TN, false, false>), dim3(r.tiles), dim3(NT), lds, s, a, r.epi);
   }
   return check_launch();
 }
 
 }  // namespace
 
-bool gemm1x1_eligible(const ConvArgs& a);
-int launch_gemm1x1(const ConvArgs& a, int cfg, int epi, hipStream_t s);
-int launch_gemm1x1_split(const ConvArgs& a, int cfg, int epi, hipStream_t s);
-int launch_gemm1x1_split_wide(const ConvArgs& a, int cfg, int epi, hipStream_t s);
-int gemm1x1_split_num_cfgs();
-int gemm1x1_num_cfgs();
-bool conv_is_skinny(const ConvArgs& a);
-int launch_conv_splitk(const ConvArgs& a, hipStream_t s);
-int launch_conv_halo(const ConvArgs& a, int cfg, int epi, hipStream_t s);
-bool conv_stem_eligible(const ConvArgs& a);
-int launch_conv_stem(const ConvArgs& a, hipStream_t s);
-
-// cfg 0..8: general implicit-GEMM kernel; cfg 9..17: the same tile shapes on the LDS-DMA kernel
-int conv_igemm_num_cfgs() { return kNumCfgs + gemm1x1_num_cfgs(); }
-
-// Default tiling when the caller does not autotune (measured on MI355X, tools/bench_ops.py): four waves
-// side by side along M with narrow per-wave tiles (more resident waves per SIMD) beat the 2x2-wave layouts;
-// memory/epilogue-bound shapes (tiny K or tiny M) want the narrowest tile.
-int conv_igemm_pick_cfg(int M, int Cout) {
-  const int np = (Cout + 31) / 32 * 32;
-  auto blocks = [&](int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((np + bn - 1) / bn); };
-  int bn = 32;
-  if (np % 96 == 0) bn = 96;
-  else if (np % 64 == 0) bn = 64;
-  if (bn == 96) return blocks(128, 96) >= 512 ? 2 : (blocks(128, 32) >= 512 ? 4 : 7);
-  if (bn == 64) return blocks(128, 64) >= 512 ? 3 : (blocks(128, 32) >= 512 ? 4 : 7);
-  if (blocks(128, 32) >= 512) return 4;
-  if (blocks(64, 32) >= 256) return 7;
-  return 8;
-}
-
 int launch_conv_igemm(const ConvArgs& a, int cfg, hipStream_t s) {
-  if (a.N <= 0 || a.Cin <= 0 || a.Cout <= 0 || a.OH <= 0 || a.OW <= 0) return DH_EINVAL;
-  if (a.Kp % BK != 0 || a.Np % 32 != 0 || a.Kp < a.K || a.Np < a.Cout || a.K != a.KH * a.KW * a.Cin)
-    return DH_EINVAL;
-  if ((long long)a.N * a.H * a.W > 0x7fffffffLL || (long long)a.N * a.OH * a.OW * (a.up2 ? 4 : 1) > 0x7fffffffLL)
-    return DH_EINVAL;
-  if (a.x_u8 && a.in_lut == nullptr) return DH_EINVAL;
-  if (a.w_split < 0 || a.w_split > 7) return DH_EINVAL;
-  // tiny output, long reduction: the in-work-group split-K kernel, whatever tiling was asked for (shape rule: the
-  // result bits of a layer must not depend on a timing-based choice)
-  if (a.y_pool != nullptr) {             // pooled second output: one image row per wave (pairs of waves pool), or [r06] two /
-                                         // four whole image rows per wave (OW = 16 / 8: the wave pools alone)
-    const bool ok = (a.OW == 32 || ((a.OW == 16 || a.OW == 8) && (a.OH * a.OW) % 32 == 0)) && a.OH % 2 == 0 && !a.up2 && !a.x_u8 && a.ldyp % 4 == 0 && a.Cout % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(a.y_pool) & 15) == 0 && a.ldy % 4 == 0 && a.w_split != 2 &&
-                    (reinterpret_cast<uintptr_t>(a.y) & 15) == 0 && !conv_is_skinny(a);
-    if (!ok) return DH_EUNSUPPORTED;
-  }
-  if (a.x_resample && !conv_is_skinny(a)) return DH_EUNSUPPORTED;   // (resampling on load: the skinny-conv kernel only)
-  if (conv_is_skinny(a)) {
-    if (a.res2_down) return DH_EUNSUPPORTED;          // (the split-K kernel has its own, simpler epilogue)
-    return cfg < kNumCfgs + gemm1x1_num_cfgs() ? launch_conv_splitk(a, s) : DH_EINVAL;
-  }
-  // first layer (3 input channels, stride 2): its own kernel, by a rule on the layer's geometry like the split-K layers --
-  // it pairs the k values of an MFMA differently from the tap-major kernels, so its last bits differ from theirs and a
-  // layer must never move between the two on a timing-based choice
-  if (conv_stem_eligible(a)) return cfg < kNumCfgs + gemm1x1_num_cfgs() ? launch_conv_stem(a, s) : DH_EINVAL;
-  const int epi = (a.Cout % 4 == 0) && (a.ldy % 4 == 0) && al16(a.y) &&
-                  (a.res1 == nullptr || (a.ldr1 % 4 == 0 && al16(a.res1))) &&
-                  (a.res2 == nullptr || (a.ldr2 % 4 == 0 && al16(a.res2))) &&
-                  (a.post_scale == nullptr || (al16(a.post_scale) && al16(a.post_shift)));
-  if (a.y_pool != nullptr && !epi) return DH_EUNSUPPORTED;
-  if (a.w_split == 2) return launch_conv_halo(a, cfg, epi_with_direct(a, epi, false), s);   // chunk-major fp32 packing: the halo-resident kernel only
-  if (cfg < 0 && a.y_pool != nullptr) {
-    cfg = conv_igemm_pick_cfg(a.N * a.OH * a.OW, a.Cout);
-    if (cfg == 8 && a.OW == 32) cfg = 7;  // 32 x 32 has no wave pair
-    if (cfg == 0 || cfg == 1) cfg = 2;    // 64-row waves do not pool
-    if (!a.w_split && gemm1x1_eligible(a)) cfg += kNumCfgs;
-  }
-  if (cfg < 0)
-    cfg = conv_igemm_pick_cfg(a.N * a.OH * a.OW, a.Cout) + (!a.w_split && !a.x_u8 && gemm1x1_eligible(a) ? kNumCfgs : 0);
-  if (!a.w_split && cfg >= kNumCfgs + gemm1x1_num_cfgs()) return DH_EINVAL;
-  if (a.x_u8 && cfg >= kNumCfgs) return DH_EUNSUPPORTED;
-  if (a.w_split >= 5) {                  // the extended split-bf16 scope (5 / 6 / 7): its own rule, refused layers run on no other kernel
-    if (cfg >= gemm1x1_split_num_cfgs()) return DH_EINVAL;
-    return launch_gemm1x1_split_wide(a, cfg, epi, s);
-  }
-  if (a.w_split) {                       // split-bf16 weights (1 / 3 / 4: three / two / one part): only the LDS-DMA GEMM family reads that packing
-    if (a.x_u8 || !gemm1x1_eligible(a)) return DH_EUNSUPPORTED;
-    if (cfg >= gemm1x1_split_num_cfgs()) return DH_EINVAL;
-    if (a.up2 && cfg == 0) cfg = 2;
-    return launch_gemm1x1_split(a, cfg, epi, s);
-  }
-  if (cfg >= kNumCfgs) {
-    cfg -= kNumCfgs;
-    if (a.up2 && cfg == 0) cfg = 2;
-    return launch_gemm1x1(a, cfg, epi_with_direct(a, epi), s);   // interior tiles: epilogue straight from the accumulators
-  }
-  if (a.up2 && cfg == 0) cfg = 2;  // 128x192 + fused up-sampling epilogue exceeds the register budget
-  const bool vec4 = !a.x_u8 && (a.Cin % 4 == 0) && (a.ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) &&
-                    (a.pre_scale == nullptr || (((reinterpret_cast<uintptr_t>(a.pre_scale) |
-                                                  reinterpret_cast<uintptr_t>(a.pre_shift)) & 15) == 0));
-  switch (cfg) {
-    case 0: return launch_cfg<2, 2, 2, 3>(a, vec4, epi, s);
-    case 1: return launch_cfg<2, 2, 2, 2>(a, vec4, epi, s);
-    case 2: return launch_cfg<4, 1, 1, 3>(a, vec4, epi, s);
-    case 3: return launch_cfg<4, 1, 1, 2>(a, vec4, epi, s);
-    case 4: return launch_cfg<4, 1, 1, 1>(a, vec4, epi, s);
-    case 5: return launch_cfg<2, 1, 1, 3>(a, vec4, epi, s);
-    case 6: return launch_cfg<2, 1, 1, 2>(a, vec4, epi, s);
-    case 7: return launch_cfg<2, 1, 1, 1>(a, vec4, epi, s);
-    case 8: return launch_cfg<1, 1, 1, 1>(a, vec4, epi, s);
+  const ConvRoute r = conv_route(a, cfg);
+  if (r.rc != DH_OK) return r.rc;
+  ConvArgs b = a;                        // the split kernels of the extended scope's codes are those of 1 / 3 / 4
+  if (a.w_split >= 5) b.w_split = conv_split_wide_base(a.w_split);
+  switch (r.kernel) {
+    case DH_CONV_GENERAL:
+      return dispatch_tile<kNumF32Cfgs>(r.tile_cfg, [&](auto c) {
+        constexpr GemmTile t = kGemmTiles[decltype(c)::value];
+        return launch_cfg<t.wm, t.wn, t.tm, t.tn>(a, r, s);
+      });
+    case DH_CONV_DMA: return launch_gemm1x1(a, r, s);
+    case DH_CONV_SPLIT: return launch_gemm1x1_split(b, r, s);
+    case DH_CONV_SPLIT_EXT: return launch_gemm1x1_split_ext(b, r, s);
+    case DH_CONV_HALO: return launch_conv_halo(a, r, s);
+    case DH_CONV_SKINNY: return launch_conv_splitk(a, r, s);
+    case DH_CONV_FIRST_LAYER: return launch_conv_stem(a, r, s);
   }
   return DH_EINVAL;
 }

@@ -27,7 +27,7 @@
 namespace dh {
 namespace {
 
-constexpr int SK_MAX_CIN = 4096; // prologue table in LDS: 2 x Cin floats
+constexpr int SK_MAX_CIN = kSkinnyMaxCin;
 
 // RS = dh_conv_args.x_resample [r06]: 0 = x as it is; 1 = x is stored at HALF resolution and read as UpSampling2D((2, 2))(x)
 // (input pixel (h, w) = x(h / 2, w / 2)); 2 / 3 = x is stored at DOUBLE resolution and read through MaxPooling2D((2, 2)) /
@@ -339,20 +339,6 @@ int launch_skinny(const ConvArgs& a, unsigned tiles, bool vec, hipStream_t s) {
 
 }  // namespace
 
-// Shape rule -- deterministic, independent of timing, of the batch size and of buffer alignment (the bits of a layer
-// must not depend on any of them): at most 256 output positions per frame / clip, at most 256 output channels, a
-// reduction of at least 64 (shorter ones are one or two K-steps of the general kernel anyway).  [r05: was K >= 768 and
-// Cin % 4 == 0 -- the action heads' 1x1 / 3x3 convolutions with K = 70 .. 720 ran 15-33 us on one wave per tile.]
-bool conv_is_skinny(const ConvArgs& a) {
-  if (a.x_u8 || a.w_split) return false;
-  // kernel extent: `locate` decodes tap -> (kh, kw) as (tap * magic_kw) >> 16, exact while tap * KW < 2^16 -- KH * KW < 256
-  // keeps tap < 256 and KW < 256 (KW < 256 alone admitted KW = 255, KH >= 2, where tap >= 258 decodes wrong)
-  // DEEPHAR_SKINNY_MIN_K: A/B aid for the rule's K threshold (read once; planner.split_k_rule reads the same variable)
-  static const int min_k = [] { const char* e = getenv("DEEPHAR_SKINNY_MIN_K"); return e != nullptr ? atoi(e) : 64; }();
-  return a.OH * a.OW <= 256 && a.K >= min_k && a.Cout <= 256 && a.Cin >= 2 && a.Cin <= SK_MAX_CIN && a.KH >= 1 && a.KW >= 1 &&
-         (long long)a.KH * a.KW < 256 && (long long)a.K * a.Cin < (1ll << 31);
-}
-
 // waves per tile: from K alone (16 k per quad, eight quads per wave and chunk)
 int conv_skinny_waves(int Kp) {
   const int quads = Kp / 16;
@@ -427,20 +413,11 @@ int launch_conv_splitk_seg(const ConvArgs& a, const ConvSeg& seg, hipStream_t s)
   }
 }
 
-int launch_conv_splitk(const ConvArgs& a, hipStream_t s) {
-  const long long M = (long long)a.N * a.OH * a.OW;
-  const long long tiles = ((M + 15) / 16) * ((a.Cout + 15) / 16);
-  if (tiles <= 0 || tiles > 0x7fffffffLL || (long long)a.H * a.W * a.ldx * (a.x_resample >= 2 ? 4 : 1) > 0x7fffffffLL ||
-      a.Kp % 16 != 0)
-    return DH_EINVAL;
-  if (a.x_resample < 0 || a.x_resample > 3 || (a.x_resample == 1 && ((a.H | a.W) & 1))) return DH_EINVAL;
-  // (the vector form is a property of the layer wherever the engine lays tensors out 16-byte aligned; both forms load
-  //  the same values and run the same arithmetic: same bits)
-  const bool vec = a.Cin % 4 == 0 && a.ldx % 4 == 0 && al16(a.x);
+int launch_conv_splitk(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
   switch (conv_skinny_waves(a.Kp)) {
-    case 16: return launch_skinny<16>(a, (unsigned)tiles, vec, s);
-    case 8: return launch_skinny<8>(a, (unsigned)tiles, vec, s);
-    default: return launch_skinny<4>(a, (unsigned)tiles, vec, s);
+    case 16: return launch_skinny<16>(a, r.tiles, r.vec4 != 0, s);
+    case 8: return launch_skinny<8>(a, r.tiles, r.vec4 != 0, s);
+    default: return launch_skinny<4>(a, r.tiles, r.vec4 != 0, s);
   }
 }
 

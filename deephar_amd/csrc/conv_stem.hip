@@ -22,7 +22,6 @@
 namespace dh {
 namespace {
 
-constexpr int kStemOW = 128;
 
 template <int KH, int KW, int TN, bool U8>
 __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const ConvArgs p, const int pairs_per_wg) {
@@ -189,48 +188,31 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const ConvArgs p, con
 }
 
 template <int KH, int KW, int TN, bool U8>
-int launch_stem_variant(const ConvArgs& a, hipStream_t s) {
+int launch_stem_variant(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
   constexpr int C = 3, KL = KW * C, KLP = (KL + 1) & ~1;
   constexpr int RP = ((kStemOW - 1) * 2 + KW) * C + 3, HR = KH + 2;
   constexpr size_t lds = (size_t)(KH * KLP * TN * 32 + HR * RP + (U8 ? 3 * 256 : 0)) * sizeof(float);
   static_assert(2 * lds <= 160 * 1024, "two work-groups per CU");
-  const int pairs = a.OH / 2;
-  const int ppw = pairs % 4 == 0 ? 4 : (pairs % 2 == 0 ? 2 : 1);
-  const long long blocks = (long long)a.N * (pairs / ppw);
-  if (blocks <= 0 || blocks > 0x7fffffffLL) return DH_EINVAL;
   auto kern = conv_stem_kernel<KH, KW, TN, U8>;
   if (lds > 64 * 1024) {
     static LdsLimit lim;
     lim.raise((const void*)kern, (int)lds);
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, s, a, ppw);
+  hipLaunchKernelGGL(kern, dim3(r.tiles), dim3(256), lds, s, a, conv_stem_pairs_per_wg(a));
   return check_launch();
 }
 
 template <int KH, int KW, int TN>
-int launch_stem_tn(const ConvArgs& a, hipStream_t s) {
-  return a.x_u8 ? launch_stem_variant<KH, KW, TN, true>(a, s) : launch_stem_variant<KH, KW, TN, false>(a, s);
+int launch_stem_tn(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  return a.x_u8 ? launch_stem_variant<KH, KW, TN, true>(a, r, s) : launch_stem_variant<KH, KW, TN, false>(a, r, s);
 }
 
 }  // namespace
 
-// The layers this kernel takes (a rule on the layer's geometry; launch_conv_igemm asks it for every launch):
-// 3 dense input channels, stride 2, 3x3 or 7x7, 128 output columns, an even number of output rows, 32 or 64 output
-// channels, fp32 tap-major weights, BN / ReLU epilogue only.
-bool conv_stem_eligible(const ConvArgs& a) {
-  const bool geom = a.Cin == 3 && a.ldx == 3 && a.SH == 2 && a.SW == 2 && a.KH == a.KW && (a.KH == 3 || a.KH == 7) &&
-                    a.OW == kStemOW && (a.OH & 1) == 0 && (a.Cout == 32 || a.Cout == 64) && a.PT >= 0 && a.PL >= 0 &&
-                    a.PL <= a.KW && a.K == a.KH * a.KW * 3;
-  const bool plain = a.pre_scale == nullptr && !a.pre_relu && a.res1 == nullptr && a.res2 == nullptr && !a.up2 &&
-                     a.y_pool == nullptr && a.w_split == 0 && (!a.x_u8 || a.in_lut != nullptr);
-  const bool fits = (long long)a.N * a.OH * a.OW * a.ldy * 4 < 0x7fffffffLL && (reinterpret_cast<uintptr_t>(a.y) & 3) == 0;
-  return geom && plain && fits;
-}
-
-int launch_conv_stem(const ConvArgs& a, hipStream_t s) {
-  if (!conv_stem_eligible(a)) return DH_EUNSUPPORTED;
-  if (a.KH == 3) return a.Cout == 32 ? launch_stem_tn<3, 3, 1>(a, s) : launch_stem_tn<3, 3, 2>(a, s);
-  return a.Cout == 32 ? launch_stem_tn<7, 7, 1>(a, s) : launch_stem_tn<7, 7, 2>(a, s);
+// The layers this kernel takes: conv_stem_eligible (conv_rules.h)
+int launch_conv_stem(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  if (a.KH == 3) return a.Cout == 32 ? launch_stem_tn<3, 3, 1>(a, r, s) : launch_stem_tn<3, 3, 2>(a, r, s);
+  return a.Cout == 32 ? launch_stem_tn<7, 7, 1>(a, r, s) : launch_stem_tn<7, 7, 2>(a, r, s);
 }
 
 }  // namespace dh

@@ -35,7 +35,7 @@ int launch_convt_variant(const ConvArgs& a, int vec, int cb, unsigned tiles, hip
 template <int WM, int WN, int TM, int TN>
 int launch_convt_cfg(const ConvArgs& a, int vec, int cb, hipStream_t s) {
   unsigned t;
-  if (gemm_tile_count<WM * TM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
+  if (gemm_tile_count(a, WM * TM * 32, WN * TN * 32, &t) != DH_OK) return DH_EINVAL;
   if (a.pre_scale != nullptr)
     return a.pre_relu ? launch_convt_variant<WM, WN, TM, TN, true, true>(a, vec, cb, t, s)
                       : launch_convt_variant<WM, WN, TM, TN, false, true>(a, vec, cb, t, s);

@@ -42,7 +42,7 @@ int launch_convts_variant(const ConvArgs& a, int vec, int cb, unsigned tiles, hi
 template <int P, int WM, int WN, int TN>
 int launch_convts_cfg(const ConvArgs& a, int vec, int cb, hipStream_t s) {
   unsigned t;
-  if (gemm_tile_count<WM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
+  if (gemm_tile_count(a, WM * 32, WN * TN * 32, &t) != DH_OK) return DH_EINVAL;
   if (a.pre_scale != nullptr)
     return a.pre_relu ? launch_convts_variant<P, WM, WN, TN, true, true>(a, vec, cb, t, s)
                       : launch_convts_variant<P, WM, WN, TN, false, true>(a, vec, cb, t, s);

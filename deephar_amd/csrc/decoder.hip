@@ -716,43 +716,56 @@ __global__ __launch_bounds__(256) void global_maxmin_softmax_kernel(const float*
 
 }  // namespace
 
-int launch_softargmax2d(const SamArgs& a, hipStream_t s) {
-  if (a.F <= 0 || a.C <= 0 || a.H <= 0 || a.W <= 0 || a.h == nullptr || a.gx == nullptr || a.gy == nullptr)
-    return DH_EINVAL;
-  const long long blocks16 = (long long)a.F * ((a.C + 15) / 16);
-  const long long blocks4 = (long long)a.F * ((a.C + 3) / 4);
-  if (blocks4 > 0x7fffffffLL) return DH_EINVAL;
-  constexpr size_t kMaxSlab = 128 * 1024;     // 32x32x16 maps need 64 KB: above the default dynamic-LDS limit
-  static LdsLimit lim;
-  lim.raise((const void*)softargmax2d_kernel<16, true>, (int)kMaxSlab);
-  const bool wide = blocks16 >= 1024;
-  const int g = wide ? 16 : 4;
-  const size_t slab = ((size_t)a.H * a.W * g + a.W + a.H) * sizeof(float);
-  const dim3 grid((unsigned)(wide ? blocks16 : blocks4));
-  if (slab > (wide ? kMaxSlab : (size_t)60 * 1024)) {
-    if (wide) hipLaunchKernelGGL((softargmax2d_kernel<16, false>), grid, dim3(NTH), 0, s, a);
-    else hipLaunchKernelGGL((softargmax2d_kernel<4, false>), grid, dim3(NTH), 0, s, a);
-  } else if (wide) {
-    hipLaunchKernelGGL((softargmax2d_kernel<16, true>), grid, dim3(NTH), slab, s, a);
+// ---- the 2-D read-outs' launch decision, from the arguments alone (exported as dh_softargmax2d_route) -----------------------
+constexpr long long kSamWideBlocks = 1024;          // 16 channels per work-group once F * ceil(C / 16) fills the chip, else 4
+constexpr size_t kSamMaxSlab = 128 * 1024;          // LDS slab of the 16-channel kernels (32x32x16 maps need 64 KB: above the default
+                                                    // dynamic-LDS limit); larger maps are read from memory / refused with context
+constexpr size_t kSamMaxSlabNarrow = 60 * 1024;     // the same for the 4-channel kernel, inside the default limit
+static size_t sam_slab_bytes(const SamArgs& a, int g) { return ((size_t)a.H * a.W * g + a.W + a.H) * sizeof(float); }
+
+dh_sam_route sam_route(const SamArgs& a, int J, int nctx) {
+  dh_sam_route r = {DH_OK, 0, 0, DH_OK};
+  const bool maps = a.h != nullptr && a.gx != nullptr && a.gy != nullptr;
+  if (a.F <= 0 || a.C <= 0 || a.H <= 0 || a.W <= 0 || !maps || (long long)a.F * ((a.C + 3) / 4) > 0x7fffffffLL) {
+    r.rc = DH_EINVAL;
   } else {
-    hipLaunchKernelGGL((softargmax2d_kernel<4, true>), grid, dim3(NTH), slab, s, a);
+    const bool wide = (long long)a.F * ((a.C + 15) / 16) >= kSamWideBlocks;
+    r.channels = wide ? 16 : 4;
+    r.staged = sam_slab_bytes(a, r.channels) <= (wide ? kSamMaxSlab : kSamMaxSlabNarrow);
+  }
+  if (a.F <= 0 || a.H <= 0 || a.W <= 0 || J <= 0 || nctx < 1 || nctx > 3 || !maps || a.C != J * (1 + nctx)) r.ctx_rc = DH_EINVAL;
+  else if (a.xy != nullptr || a.conf_prob != nullptr || a.prob != nullptr || a.gmax != nullptr) r.ctx_rc = DH_EUNSUPPORTED;
+  // float4 staging: the joints' and the contexts' channel quads are 16-byte aligned runs of the pixel; no unstaged variant
+  else if (J % 4 || a.ldh % 4 || (reinterpret_cast<uintptr_t>(a.h) & 15) || sam_slab_bytes(a, CG) > kSamMaxSlab) r.ctx_rc = DH_EUNSUPPORTED;
+  return r;
+}
+
+int launch_softargmax2d(const SamArgs& a, hipStream_t s) {
+  const dh_sam_route r = sam_route(a, 0, 0);
+  if (r.rc != DH_OK) return r.rc;
+  static LdsLimit lim;
+  lim.raise((const void*)softargmax2d_kernel<16, true>, (int)kSamMaxSlab);
+  const size_t slab = r.staged ? sam_slab_bytes(a, r.channels) : 0;
+  const dim3 grid((unsigned)(a.F * ((a.C + r.channels - 1) / r.channels)));
+  if (r.channels == 16) {
+    if (r.staged) hipLaunchKernelGGL((softargmax2d_kernel<16, true>), grid, dim3(NTH), slab, s, a);
+    else hipLaunchKernelGGL((softargmax2d_kernel<16, false>), grid, dim3(NTH), 0, s, a);
+  } else {
+    if (r.staged) hipLaunchKernelGGL((softargmax2d_kernel<4, true>), grid, dim3(NTH), slab, s, a);
+    else hipLaunchKernelGGL((softargmax2d_kernel<4, false>), grid, dim3(NTH), 0, s, a);
   }
   return check_launch();
 }
 
 int launch_softargmax2d_context(const SamArgs& a, int J, int nctx, float agg_alpha, float* y, int ldy, hipStream_t s) {
-  if (a.F <= 0 || a.H <= 0 || a.W <= 0 || J <= 0 || nctx < 1 || nctx > 3 || y == nullptr || ldy < 2) return DH_EINVAL;
-  if (a.h == nullptr || a.gx == nullptr || a.gy == nullptr || a.C != J * (1 + nctx)) return DH_EINVAL;
-  if (a.xy != nullptr || a.conf_prob != nullptr || a.prob != nullptr || a.gmax != nullptr) return DH_EUNSUPPORTED;
-  // float4 staging: the joints' and the contexts' channel quads are 16-byte aligned runs of the pixel
-  if (J % 4 || a.ldh % 4 || (reinterpret_cast<uintptr_t>(a.h) & 15)) return DH_EUNSUPPORTED;
-  const size_t slab = ((size_t)a.H * a.W * CG + a.W + a.H) * sizeof(float);
-  if (slab > 128 * 1024) return DH_EUNSUPPORTED;
+  if (y == nullptr || ldy < 2) return DH_EINVAL;
+  const dh_sam_route r = sam_route(a, J, nctx);
+  if (r.ctx_rc != DH_OK) return r.ctx_rc;
   // 16 channel lanes x 64 pixel lanes: sixteen pixels per thread and pass, like the four-channel soft-argmax variant
   constexpr int NT = 1024;
   static LdsLimit lim;
-  lim.raise((const void*)softargmax2d_ctx_kernel<NT>, 128 * 1024);
-  hipLaunchKernelGGL(softargmax2d_ctx_kernel<NT>, dim3((unsigned)(a.F * ((J + 3) / 4))), dim3(NT), slab, s, a, J, nctx,
+  lim.raise((const void*)softargmax2d_ctx_kernel<NT>, (int)kSamMaxSlab);
+  hipLaunchKernelGGL(softargmax2d_ctx_kernel<NT>, dim3((unsigned)(a.F * ((J + 3) / 4))), dim3(NT), sam_slab_bytes(a, CG), s, a, J, nctx,
                      agg_alpha, y, ldy);
   return check_launch();
 }

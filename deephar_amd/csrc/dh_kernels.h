@@ -3,11 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "deephar_hip.h"
+#include "conv_route.h"
 
 namespace dh {
 
-using ConvArgs = dh_conv_args;
 using ConvSeg = dh_conv_seg;
 using DwArgs = dh_dw_args;
 using DwsArgs = dh_dw_strided;
@@ -23,19 +22,15 @@ __device__ __forceinline__ int xcd_order(int b, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
 }
 
+// dh_conv2d_f32: conv_route, then the family launcher the route names -- each takes the route as decided
 int launch_conv_igemm(const ConvArgs& a, int cfg, hipStream_t s);
+int launch_gemm1x1(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
+int launch_gemm1x1_split(const ConvArgs& a, const ConvRoute& r, hipStream_t s);        // a.w_split: 1 / 3 / 4
+int launch_gemm1x1_split_ext(const ConvArgs& a, const ConvRoute& r, hipStream_t s);    // a.w_split: 1 / 3 / 4
+int launch_conv_halo(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
+int launch_conv_splitk(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
+int launch_conv_stem(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
 int launch_normalize_u8(const unsigned char* x, const float* lut, float* y, long long n_pixels, int C, hipStream_t s);
-int conv_igemm_pick_cfg(int M, int Cout);
-int conv_igemm_num_cfgs();
-bool conv_is_skinny(const ConvArgs& a);
-bool conv_stem_eligible(const ConvArgs& a);
-int gemm1x1_split_num_cfgs();
-bool gemm1x1_split_eligible(const ConvArgs& a);
-int conv_split_parts(int w_split);   // bf16 parts per operand of a split packing (w_split 1 / 3 / 4 -> 3 / 2 / 1), else 0
-bool gemm1x1_split_wide_eligible(const ConvArgs& a);   // the extended scope, w_split 5 / 6 / 7 (gemm1x1s_ext.hip)
-int conv_split_wide_base(int w_split);                 // 5 / 6 / 7 -> 1 / 3 / 4 (the same packing and arithmetic), else 0
-bool conv_halo_eligible(const ConvArgs& a);
-int conv_halo_num_cfgs();
 int launch_dwconv(const DwArgs& a, hipStream_t s);
 int launch_dwconv_strided(const DwsArgs& a, hipStream_t s);
 int launch_convt2x2(const ConvArgs& gemm, int cb, int cfg, hipStream_t s);
@@ -50,6 +45,7 @@ int launch_pool(const PoolArgs& a, hipStream_t s);
 int launch_upsample2x_add(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int N, int H,
                           int W, int C, hipStream_t s);
 int launch_eltwise(const EltArgs& a, hipStream_t s);
+dh_sam_route sam_route(const SamArgs& a, int J, int nctx);      // decoder.hip: what the next two will do
 int launch_softargmax2d(const SamArgs& a, hipStream_t s);
 int launch_softargmax2d_context(const SamArgs& a, int J, int nctx, float agg_alpha, float* y, int ldy, hipStream_t s);
 int launch_context_agg(const float* ys, const float* yc, const float* pc, float* y, int F, int J, int nctx,
@@ -82,15 +78,6 @@ struct LdsLimit {
     done |= bit;
   }
 };
-
-// Shared launch-side predicates.
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-// bytes a buffer descriptor may span: every 32-bit byte offset into it stays below the out-of-range offsets the kernels use
-constexpr long long kMaxBufferBytes = 0xf0000000LL;
-// a 1x1 / stride-1 / unpadded filter ...
-inline bool conv_is_1x1(const ConvArgs& a) { return a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PT == 0 && a.PL == 0; }
-// ... over a map it leaves the size of, with 16-byte channel runs: the pointwise form of the LDS-DMA GEMM family
-inline bool conv_is_pointwise(const ConvArgs& a) { return conv_is_1x1(a) && a.H == a.OH && a.W == a.OW && a.Cin % 4 == 0; }
 
 inline int check_launch() {
   hipError_t e = hipGetLastError();

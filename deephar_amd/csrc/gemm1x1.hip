@@ -63,50 +63,28 @@ int launch_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t s) {
   return check_launch();
 }
 
+// every tiling in its forms: fused up-sampling (where the tiling has it), K x K, BN prologue, plain -- each with and without ReLU
 template <int WM, int WN, int TM, int TN>
-int launch_cfg(const ConvArgs& a, int epi, hipStream_t s) {
-  unsigned t;
-  if (gemm_tile_count<WM * TM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
-  if (a.y_pool != nullptr && !conv_epilogue_pools_for<WM, TM, false>(a)) return DH_EUNSUPPORTED;
-  if (a.up2) {
-    if constexpr (TM * TN >= 6) {
-      return DH_EUNSUPPORTED;
-    } else {
-      return a.pre_relu ? launch_variant<WM, WN, TM, TN, true, true>(a, epi, t, s)
-                        : launch_variant<WM, WN, TM, TN, true, false>(a, epi, t, s);
-    }
+int launch_cfg(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  if constexpr (tile_has_up2(GemmTile{WM, WN, TM, TN})) {
+    if (a.up2)
+      return a.pre_relu ? launch_variant<WM, WN, TM, TN, true, true>(a, r.epi, r.tiles, s)
+                        : launch_variant<WM, WN, TM, TN, true, false>(a, r.epi, r.tiles, s);
   }
   if (!conv_is_1x1(a))
-    return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true, true>(a, epi, t, s)
-                      : launch_variant<WM, WN, TM, TN, false, false, true>(a, epi, t, s);
+    return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true, true>(a, r.epi, r.tiles, s)
+                      : launch_variant<WM, WN, TM, TN, false, false, true>(a, r.epi, r.tiles, s);
   if (a.pre_scale != nullptr)       // BatchNormalization (+ ReLU) prologue on the A fragments
-    return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true, false, true>(a, epi, t, s)
-                      : launch_variant<WM, WN, TM, TN, false, false, false, true>(a, epi, t, s);
-  return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true>(a, epi, t, s)
-                    : launch_variant<WM, WN, TM, TN, false, false>(a, epi, t, s);
+    return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true, false, true>(a, r.epi, r.tiles, s)
+                      : launch_variant<WM, WN, TM, TN, false, false, false, true>(a, r.epi, r.tiles, s);
+  return a.pre_relu ? launch_variant<WM, WN, TM, TN, false, true>(a, r.epi, r.tiles, s)
+                    : launch_variant<WM, WN, TM, TN, false, false>(a, r.epi, r.tiles, s);
 }
-
-}  // namespace
-
-bool gemm1x1_eligible(const ConvArgs& a) {
-  const bool aligned = a.ldx % 4 == 0 && al16(a.x) && al16(a.w);
-  const bool pointwise = conv_is_pointwise(a);
-  // K x K: a K-step must not straddle filter taps, the up-sampling epilogue is only built for the pointwise form
-  const bool kxk = a.Cin % BK == 0 && !a.up2 && a.KH >= 1 && a.KW >= 1 && a.SH >= 1 && a.SW >= 1 && a.PT >= 0 &&
-                   a.PL >= 0;
-  // a BatchNormalization prologue: the plain pointwise form only (no zero padding to apply it around, no fused
-  // up-sampling), fp32 weights, tables that fit LDS
-  const bool pre_ok = a.pre_scale == nullptr || (pointwise && !a.up2 && a.w_split == 0 && a.Kp <= kMaxPreKp);
-  const bool fits32 = (long long)a.N * a.H * a.W * a.ldx * 4 <= kMaxBufferBytes;   // 32-bit buffer offsets
-  return aligned && pre_ok && fits32 && (pointwise || kxk);
-}
-
-namespace {
 
 template <int WM, int KS, int DNT, int MAXT, int MAXN>
 int launch_group(const ConvArgs& a, int epi, const DwArgs& d, const dwl::DwLdsGeom& g, hipStream_t s) {
   unsigned tiles;
-  if (gemm_tile_count<WM * 32, 32>(a, &tiles) != DH_OK || (long long)tiles + g.blocks > 0x7fffffffLL) return DH_EINVAL;
+  if (gemm_tile_count(a, WM * 32, 32, &tiles) != DH_OK || (long long)tiles + g.blocks > 0x7fffffffLL) return DH_EINVAL;
   const size_t lds = std::max(gemm_f32_lds(WM, 1, 1, 1, true, a.Kp).launch, g.lds);
   auto kern = conv_dw_group_kernel<WM, true, true, KS, DNT, MAXT, MAXN, true, true>;
   static LdsLimit lim;
@@ -123,8 +101,7 @@ int launch_group(const ConvArgs& a, int epi, const DwArgs& d, const dwl::DwLdsGe
 // 5x5 depthwise convolution `d` (BatchNormalization + ReLU prologue, LDS-tiled kernel) in one launch; DH_EUNSUPPORTED for
 // anything else -- the caller then launches the two on their own, with the same result bits.
 int launch_conv_dw_group(const ConvArgs& a, const DwArgs& d, hipStream_t s) {
-  if (a.N <= 0 || a.Cin <= 0 || a.Cout <= 0 || a.OH <= 0 || a.OW <= 0 || d.N <= 0 || d.C <= 0) return DH_EINVAL;
-  if (a.Kp % BK != 0 || a.Np % 32 != 0 || a.Kp < a.K || a.Np < a.Cout || a.K != a.KH * a.KW * a.Cin) return DH_EINVAL;
+  if (conv_check_packing(a) != DH_OK || d.N <= 0 || d.C <= 0) return DH_EINVAL;
   if (!(conv_is_1x1(a) && a.H == a.OH && a.W == a.OW) || a.up2 || a.y_pool != nullptr || a.x_u8 || a.w_split || a.pre_scale == nullptr || !a.pre_relu ||
       a.Kp > kMaxPreKp || !gemm1x1_eligible(a) || conv_is_skinny(a) || conv_stem_eligible(a))
     return DH_EUNSUPPORTED;
@@ -132,10 +109,7 @@ int launch_conv_dw_group(const ConvArgs& a, const DwArgs& d, hipStream_t s) {
   dwl::DwLdsGeom g;
   if (d.KW != 5 || d.pre_scale == nullptr || !d.pre_relu || !dwl::dw_lds_geometry(d, g)) return DH_EUNSUPPORTED;
   if (d.up_in && ((d.H & 1) || (d.W & 1))) return DH_EINVAL;
-  const int epi0 = (a.Cout % 4 == 0) && (a.ldy % 4 == 0) && al16(a.y) && (a.res1 == nullptr || (a.ldr1 % 4 == 0 && al16(a.res1))) &&
-                   (a.res2 == nullptr || (a.ldr2 % 4 == 0 && al16(a.res2))) &&
-                   (a.post_scale == nullptr || (al16(a.post_scale) && al16(a.post_shift)));
-  const int epi = epi_with_direct(a, epi0);
+  const int epi = epi_with_direct(a, conv_epi_vec(a));
   const long long M = (long long)a.N * a.OH * a.OW;
   if (M > 0x7fffffffLL) return DH_EINVAL;
   // (all tilings of the family give the same bits: the group picks its own -- 128-row tiles once they fill the chip)
@@ -144,22 +118,11 @@ int launch_conv_dw_group(const ConvArgs& a, const DwArgs& d, hipStream_t s) {
   return wide ? launch_group<4, 5, 64, 6, 12>(a, epi, d, g, s) : launch_group<2, 5, 64, 6, 12>(a, epi, d, g, s);
 }
 
-int launch_gemm1x1(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  if (!gemm1x1_eligible(a)) return DH_EUNSUPPORTED;
-  switch (cfg) {
-    case 0: return launch_cfg<2, 2, 2, 3>(a, epi, s);
-    case 1: return launch_cfg<2, 2, 2, 2>(a, epi, s);
-    case 2: return launch_cfg<4, 1, 1, 3>(a, epi, s);
-    case 3: return launch_cfg<4, 1, 1, 2>(a, epi, s);
-    case 4: return launch_cfg<4, 1, 1, 1>(a, epi, s);
-    case 5: return launch_cfg<2, 1, 1, 3>(a, epi, s);
-    case 6: return launch_cfg<2, 1, 1, 2>(a, epi, s);
-    case 7: return launch_cfg<2, 1, 1, 1>(a, epi, s);
-    case 8: return launch_cfg<1, 1, 1, 1>(a, epi, s);
-  }
-  return DH_EINVAL;
+int launch_gemm1x1(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  return dispatch_tile<kNumF32Cfgs>(r.tile_cfg, [&](auto c) {
+    constexpr GemmTile t = kGemmTiles[decltype(c)::value];
+    return launch_cfg<t.wm, t.wn, t.tm, t.tn>(a, r, s);
+  });
 }
-
-int gemm1x1_num_cfgs() { return 9; }
 
 }  // namespace dh

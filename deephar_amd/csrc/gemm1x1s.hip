@@ -19,41 +19,23 @@
 // per product) or a1 b1 alone (plain bf16 operands, about 2^-8) -- i.e. 3 or 1 MFMA per 16 k instead of 6, one or no
 // residual pass in the activation split, a B stage of 4 P BN units, weights packed [K/8][P parts][Np][8].  Same K order,
 // same epilogue, bit-identical across tilings within a mode; the wide tiling below exists for P = 3 only.
-// This file is the three-part mode, the rule and the dispatch; the kernels and their launch side are gemm1x1s_launch.h, the
+// This file is the three-part mode and the dispatch (the rule: conv_rules.h, gemm1x1_split_eligible); the kernels and their launch side are gemm1x1s_launch.h, the
 // two- and one-part modes gemm1x1s_p2.hip / gemm1x1s_p1.hip (one translation unit per mode: compile time).
 // Reference layers replaced: as gemm1x1.hip (deephar/layers.py:74-80, 258-301; models/reception.py:43-98).
 #include "gemm1x1s_launch.h"
 
 namespace dh {
 
-bool gemm1x1_eligible(const ConvArgs& a);
-int launch_gemm1x1_split_p2(const ConvArgs& a, int cfg, int epi, hipStream_t s);
-int launch_gemm1x1_split_p1(const ConvArgs& a, int cfg, int epi, hipStream_t s);
+int launch_gemm1x1_split_p2(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
+int launch_gemm1x1_split_p1(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
 
-// What dh_conv2d_f32 accepts with a split packing, w_split = 1 / 3 / 4: one rule for every mode (the weight pointer itself
-// is not looked at: a binding asks before it packs).
-bool gemm1x1_split_eligible(const ConvArgs& a0) {
-  ConvArgs a = a0;
-  a.w = reinterpret_cast<const float*>(uintptr_t(16));
-  a.w_split = 0;                       // (conv_is_skinny answers for the fp32 packing)
-  if (a.x_u8 || a.pre_scale != nullptr || conv_is_skinny(a) || !gemm1x1_eligible(a)) return false;   // (no BN prologue on the split path)
-  // 32-bit byte offsets into the buffer descriptors
-  return (long long)a.N * a.H * a.W * a.ldx * 4 <= kMaxBufferBytes && (long long)a.Kp * a.Np * 6 <= kMaxBufferBytes;
-}
-
-// bf16 parts per operand of a split packing (dh_conv_args.w_split), 0 for the fp32 packings
-int conv_split_parts(int w_split) { return w_split == 1 ? 3 : (w_split == 3 ? 2 : (w_split == 4 ? 1 : 0)); }
-
-int launch_gemm1x1_split(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  if (!gemm1x1_eligible(a) || !gemm1x1_split_eligible(a)) return DH_EUNSUPPORTED;
-  switch (conv_split_parts(a.w_split)) {
-    case 3: return launch_split_parts<3>(a, cfg, epi, s);
-    case 2: return launch_gemm1x1_split_p2(a, cfg, epi, s);
-    case 1: return launch_gemm1x1_split_p1(a, cfg, epi, s);
+int launch_gemm1x1_split(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  switch (r.parts) {
+    case 3: return launch_split_parts<3>(a, r, s);
+    case 2: return launch_gemm1x1_split_p2(a, r, s);
+    case 1: return launch_gemm1x1_split_p1(a, r, s);
   }
   return DH_EINVAL;
 }
-
-int gemm1x1_split_num_cfgs() { return kNumSplitCfgs; }
 
 }  // namespace dh

@@ -16,47 +16,41 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gemm1x1s_ext_kernel(const Conv
 }
 
 template <int P, int WM, int WN, int TM, int TN, bool RELU, bool KXK, bool PRE, int NS>
-int launch_ext_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t s) {
-  constexpr size_t kMax = gemm_split_lds(P, WM, WN, TM, TN, NS, PRE, 0).limit;
-  if constexpr (kMax > 160 * 1024) {
-    return DH_EUNSUPPORTED;            // three stages of the 256-row tiles leave no room for the largest tables
+int launch_ext_variant(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  if constexpr (!tile_ext_fits(GemmTile{WM, WN, TM, TN, NS}, P, PRE)) {
+    return DH_EUNSUPPORTED;
   } else {
+    constexpr size_t kMax = gemm_split_lds(P, WM, WN, TM, TN, NS, PRE, 0).limit;
     auto kern = gemm1x1s_ext_kernel<P, WM, WN, TM, TN, RELU, KXK, PRE, NS>;
     if (kMax > 64 * 1024) {
       static LdsLimit lim;
       lim.raise((const void*)kern, (int)kMax);
     }
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), gemm_split_lds(P, WM, WN, TM, TN, NS, PRE, a.Kp).launch, s, a, epi);
+    hipLaunchKernelGGL(kern, dim3(r.tiles), dim3(WM * WN * 64), gemm_split_lds(P, WM, WN, TM, TN, NS, PRE, a.Kp).launch, s, a, r.epi);
     return check_launch();
   }
 }
 
 template <int P, int WM, int WN, int TM, int TN, int NS = 2>
-int launch_ext_cfg(const ConvArgs& a, int epi, hipStream_t s) {
-  unsigned t;
-  if (gemm_tile_count<WM * TM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
-  if (a.y_pool != nullptr && !conv_epilogue_pools_for<WM, TM, false>(a)) return DH_EUNSUPPORTED;
-  if (a.pre_scale != nullptr) {        // (a): the BN prologue exists on the pipelined loop only
-    if constexpr (TM != 1) {
-      return DH_EUNSUPPORTED;
-    } else {
-      return a.pre_relu ? launch_ext_variant<P, WM, WN, TM, TN, true, false, true, NS>(a, epi, t, s)
-                        : launch_ext_variant<P, WM, WN, TM, TN, false, false, true, NS>(a, epi, t, s);
-    }
+int launch_ext_cfg(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  if constexpr (tile_has_ext_prologue(GemmTile{WM, WN, TM, TN, NS})) {
+    if (a.pre_scale != nullptr)        // (a): the BN prologue
+      return a.pre_relu ? launch_ext_variant<P, WM, WN, TM, TN, true, false, true, NS>(a, r, s)
+                        : launch_ext_variant<P, WM, WN, TM, TN, false, false, true, NS>(a, r, s);
   }
-  return a.pre_relu ? launch_ext_variant<P, WM, WN, TM, TN, true, true, false, NS>(a, epi, t, s)
-                    : launch_ext_variant<P, WM, WN, TM, TN, false, true, false, NS>(a, epi, t, s);
+  return a.pre_relu ? launch_ext_variant<P, WM, WN, TM, TN, true, true, false, NS>(a, r, s)
+                    : launch_ext_variant<P, WM, WN, TM, TN, false, true, false, NS>(a, r, s);
 }
 
 // every tiling of one mode; the wide tiling (14, 15) is not built for these layers
 template <int P>
-int launch_ext_parts(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  return dispatch_split_tile(cfg, [&](auto tile) -> int {
-    using T = decltype(tile);
-    if constexpr (T::kWide) {
+int launch_ext_parts(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  return dispatch_tile<kNumSplitCfgs>(r.tile_cfg, [&](auto c) -> int {
+    constexpr GemmTile t = kGemmTiles[decltype(c)::value];
+    if constexpr (!tile_has_parts(t, P, true)) {
       return DH_EUNSUPPORTED;
     } else {
-      return launch_ext_cfg<P, T::WM, T::WN, T::TM, T::TN, T::NS>(a, epi, s);
+      return launch_ext_cfg<P, t.wm, t.wn, t.tm, t.tn, t.ns>(a, r, s);
     }
   });
 }

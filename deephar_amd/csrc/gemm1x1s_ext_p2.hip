@@ -1,3 +1,3 @@
 // The 'bf16x2' mode of the extended split-bf16 scope (gemm1x1s_ext.hip with 2 bf16 parts per operand) as a translation unit of its own.
 #include "gemm1x1s_ext_launch.h"
-namespace dh { int launch_gemm1x1_split_ext_p2(const ConvArgs& a, int cfg, int epi, hipStream_t s) { return launch_ext_parts<2>(a, cfg, epi, s); } }
+namespace dh { int launch_gemm1x1_split_ext_p2(const ConvArgs& a, const ConvRoute& r, hipStream_t s) { return launch_ext_parts<2>(a, r, s); } }

@@ -254,17 +254,15 @@ int launch_wide_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t 
 }
 
 template <int WM>
-int launch_wide(const ConvArgs& a, int epi, hipStream_t s) {
-  unsigned t;
-  if (gemm_tile_count<WM * 32, 192>(a, &t) != DH_OK) return DH_EINVAL;
+int launch_wide(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
   if (a.up2)
-    return a.pre_relu ? launch_wide_variant<WM, true, true, false>(a, epi, t, s)
-                      : launch_wide_variant<WM, true, false, false>(a, epi, t, s);
+    return a.pre_relu ? launch_wide_variant<WM, true, true, false>(a, r.epi, r.tiles, s)
+                      : launch_wide_variant<WM, true, false, false>(a, r.epi, r.tiles, s);
   if (!conv_is_1x1(a))
-    return a.pre_relu ? launch_wide_variant<WM, false, true, true>(a, epi, t, s)
-                      : launch_wide_variant<WM, false, false, true>(a, epi, t, s);
-  return a.pre_relu ? launch_wide_variant<WM, false, true, false>(a, epi, t, s)
-                    : launch_wide_variant<WM, false, false, false>(a, epi, t, s);
+    return a.pre_relu ? launch_wide_variant<WM, false, true, true>(a, r.epi, r.tiles, s)
+                      : launch_wide_variant<WM, false, false, true>(a, r.epi, r.tiles, s);
+  return a.pre_relu ? launch_wide_variant<WM, false, true, false>(a, r.epi, r.tiles, s)
+                    : launch_wide_variant<WM, false, false, false>(a, r.epi, r.tiles, s);
 }
 
 template <int P, int WM, int WN, int TM, int TN, bool UP2, bool RELU, bool KXK = false, int NS = 2>
@@ -281,37 +279,30 @@ int launch_variant(const ConvArgs& a, int epi, unsigned tiles, hipStream_t s) {
 }
 
 template <int P, int WM, int WN, int TM, int TN, int NS = 2>
-int launch_cfg(const ConvArgs& a, int epi, hipStream_t s) {
-  unsigned t;
-  if (gemm_tile_count<WM * TM * 32, WN * TN * 32>(a, &t) != DH_OK) return DH_EINVAL;
-  if (a.y_pool != nullptr && !conv_epilogue_pools_for<WM, TM, false>(a)) return DH_EUNSUPPORTED;
-  if (a.up2) {
-    if constexpr (TM * TN >= 6) {
-      return DH_EUNSUPPORTED;
-    } else {
-      return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, true, true, false, NS>(a, epi, t, s)
-                        : launch_variant<P, WM, WN, TM, TN, true, false, false, NS>(a, epi, t, s);
-    }
+int launch_cfg(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  if constexpr (tile_has_up2(GemmTile{WM, WN, TM, TN})) {
+    if (a.up2)
+      return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, true, true, false, NS>(a, r.epi, r.tiles, s)
+                        : launch_variant<P, WM, WN, TM, TN, true, false, false, NS>(a, r.epi, r.tiles, s);
   }
   if (!conv_is_1x1(a))
-    return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, false, true, true, NS>(a, epi, t, s)
-                      : launch_variant<P, WM, WN, TM, TN, false, false, true, NS>(a, epi, t, s);
-  return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, false, true, false, NS>(a, epi, t, s)
-                    : launch_variant<P, WM, WN, TM, TN, false, false, false, NS>(a, epi, t, s);
+    return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, false, true, true, NS>(a, r.epi, r.tiles, s)
+                      : launch_variant<P, WM, WN, TM, TN, false, false, true, NS>(a, r.epi, r.tiles, s);
+  return a.pre_relu ? launch_variant<P, WM, WN, TM, TN, false, true, false, NS>(a, r.epi, r.tiles, s)
+                    : launch_variant<P, WM, WN, TM, TN, false, false, false, NS>(a, r.epi, r.tiles, s);
 }
 
-// every tiling of one mode (P parts).  The wide tiling exists for three parts only: with fewer products per K-step its
-// fixed half-tile choreography has nothing left to hide the operand traffic under.
+// every tiling one mode (P parts) has (tile_has_parts: the wide tiling exists for three parts only)
 template <int P>
-int launch_split_parts(const ConvArgs& a, int cfg, int epi, hipStream_t s) {
-  return dispatch_split_tile(cfg, [&](auto tile) -> int {
-    using T = decltype(tile);
-    if constexpr (!T::kWide) {
-      return launch_cfg<P, T::WM, T::WN, T::TM, T::TN, T::NS>(a, epi, s);
-    } else if constexpr (P == 3) {
-      return launch_wide<T::WM>(a, epi, s);
-    } else {
+int launch_split_parts(const ConvArgs& a, const ConvRoute& r, hipStream_t s) {
+  return dispatch_tile<kNumSplitCfgs>(r.tile_cfg, [&](auto c) -> int {
+    constexpr GemmTile t = kGemmTiles[decltype(c)::value];
+    if constexpr (!tile_has_parts(t, P, false)) {
       return DH_EUNSUPPORTED;
+    } else if constexpr (t.wide) {
+      return launch_wide<t.wm>(a, r, s);
+    } else {
+      return launch_cfg<P, t.wm, t.wn, t.tm, t.tn, t.ns>(a, r, s);
     }
   });
 }

@@ -1,14 +1,14 @@
-// Launch-side arithmetic of the LDS-DMA GEMM family, stated once: the K-step, the dynamic LDS of the fp32 form (gemm1x1.hip,
-// convt2x2.hip) and of the split-bf16 form (gemm1x1s_launch.h, gemm1x1s_ext_launch.h, convt2x2s.hip), and the tilings of
-// the split-bf16 convolution kernels.
+// Launch-side arithmetic of the MFMA GEMM families, stated once: the tilings dh_conv2d_f32's tile_cfg names and what each of
+// them has a kernel for, and the dynamic LDS of the fp32 form (gemm1x1.hip, convt2x2.hip) and of the split-bf16 form
+// (gemm1x1s_launch.h, gemm1x1s_ext_launch.h, convt2x2s.hip) of the LDS-DMA GEMM.  No HIP header: conv_route.h reads the
+// table at run time, the launch templates read it in their `if constexpr` guards.
 #pragma once
 #include <algorithm>
+#include <utility>
 
-#include "conv_common.h"
+#include "conv_rules.h"
 
 namespace dh {
-
-constexpr int BK = 32;   // k values per K-step (the wide split tiling walks 16)
 
 // `launch`: dynamic LDS bytes of a launch; `limit`: what hipFuncAttributeMaxDynamicSharedMemorySize is raised to once per
 // kernel and device, so it cannot depend on the layer (LdsLimit).
@@ -32,43 +32,71 @@ constexpr GemmLds gemm_f32_lds(int WM, int WN, int TM, int TN, bool PRE, int Kp)
 constexpr GemmLds gemm_split_lds(int P, int WM, int WN, int TM, int TN, int NS, bool PRE, int Kp) {   // B: 4 k-groups x P parts x BN units
   return gemm_lds(NS * (WM * TM * 32 * BK + 4 * P * WN * TN * 32 * 4), gemm_epi_floats(WM, WN, TN), PRE, Kp, false);
 }
+constexpr size_t kMaxLds = 160 * 1024;
 
-// ---- the tilings of the split-bf16 convolution kernels: dh_conv2d_f32's tile_cfg -> per-wave tile and LDS stages ----------
-template <int WM_, int WN_, int TM_, int TN_, int NS_ = 2>
-struct SplitTile {
-  static constexpr bool kWide = false;
-  static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, NS = NS_;
+// ---- the tilings: work-group = wm x wn waves, a wave owns tm x tn MFMA tiles of 32 x 32; ns LDS stages (split kernels) -----
+struct GemmTile {
+  int wm, wn, tm, tn, ns;
+  bool wide;        // gemm1x1s_wide_kernel: wm waves of 32 x 192 (two halves of three column tiles), 16-k K-steps
+  constexpr int bm() const { return wm * tm * 32; }
+  constexpr int bn() const { return wn * tn * 32; }
 };
-template <int WM_>
-struct SplitWideTile {                   // gemm1x1s_wide_kernel: WM waves of 32 x 192, 16-k K-steps
-  static constexpr bool kWide = true;
-  static constexpr int WM = WM_;
-};
-constexpr int kNumSplitCfgs = 16;
-
-// f(tile type{}) for the tiling `cfg`, DH_EINVAL for a cfg that is none.  Every tiling of a mode gives the same bits.
-template <typename F>
-int dispatch_split_tile(int cfg, F&& f) {
-  switch (cfg) {
-    case 0: return f(SplitTile<2, 2, 2, 3>{});
-    case 1: return f(SplitTile<2, 2, 2, 2>{});
-    case 2: return f(SplitTile<4, 1, 1, 3>{});
-    case 3: return f(SplitTile<4, 1, 1, 2>{});
-    case 4: return f(SplitTile<4, 1, 1, 1>{});
-    case 5: return f(SplitTile<2, 1, 1, 3>{});
-    case 6: return f(SplitTile<2, 1, 1, 2>{});
-    case 7: return f(SplitTile<2, 1, 1, 1>{});
-    case 8: return f(SplitTile<1, 1, 1, 1>{});
+// Rows 0..8 are the tilings of the two fp32 kernels (tile_cfg 0..8: general implicit GEMM, 9..17: LDS-DMA GEMM) and of the
+// split-bf16 kernels; 9..15 exist in the split-bf16 kernels only.  Every tiling of a kernel and mode gives the same bits.
+constexpr GemmTile kGemmTiles[] = {
+    {2, 2, 2, 3, 2},  //  0: 128 x 192
+    {2, 2, 2, 2, 2},  //  1: 128 x 128
+    {4, 1, 1, 3, 2},  //  2: 128 x  96
+    {4, 1, 1, 2, 2},  //  3: 128 x  64
+    {4, 1, 1, 1, 2},  //  4: 128 x  32
+    {2, 1, 1, 3, 2},  //  5:  64 x  96
+    {2, 1, 1, 2, 2},  //  6:  64 x  64
+    {2, 1, 1, 1, 2},  //  7:  64 x  32
+    {1, 1, 1, 1, 2},  //  8:  32 x  32
     // one work-group per CU, three LDS stages: two K-steps of DMA in flight, bigger tiles = less L2 -> LDS traffic per MAC
-    case 9: return f(SplitTile<8, 1, 1, 3, 3>{});       // 256 x 96, 8 waves
-    case 10: return f(SplitTile<4, 1, 1, 3, 3>{});      // 128 x 96, 4 waves
-    case 11: return f(SplitTile<8, 1, 1, 2, 3>{});      // 256 x 64
-    case 12: return f(SplitTile<4, 2, 1, 3, 2>{});      // 128 x 192, 8 waves, two stages
-    case 13: return f(SplitTile<4, 2, 2, 3, 2>{});      // 256 x 192, 8 waves of 64 x 96
-    case 14: return f(SplitWideTile<4>{});              // 128 x 192, 4 waves of 32 x 192, 16-k K-steps
-    case 15: return f(SplitWideTile<2>{});              // 64 x 192
-  }
-  return DH_EINVAL;
+    {8, 1, 1, 3, 3},  //  9: 256 x  96, 8 waves
+    {4, 1, 1, 3, 3},  // 10: 128 x  96, 4 waves
+    {8, 1, 1, 2, 3},  // 11: 256 x  64
+    {4, 2, 1, 3, 2},  // 12: 128 x 192, 8 waves, two stages
+    {4, 2, 2, 3, 2},  // 13: 256 x 192, 8 waves of 64 x 96
+    {4, 1, 1, 6, 2, true},  // 14: 128 x 192, 4 waves of 32 x 192, 16-k K-steps
+    {2, 1, 1, 6, 2, true},  // 15:  64 x 192
+};
+constexpr int kNumF32Cfgs = 9;
+constexpr int kNumSplitCfgs = sizeof(kGemmTiles) / sizeof(kGemmTiles[0]);
+constexpr int kNumConvCfgs = 2 * kNumF32Cfgs;     // dh_conv2d_num_tile_cfgs()
+
+// What a tiling has a kernel for.
+// The epilogue can also write the 2x2 max-pooled output (dh_conv_args.y_pool) in waves pairs: every wave owns ONE 32-row
+// block = one image row at OW == 32, and the waves come in (even, odd) pairs over M.
+constexpr bool tile_pools_in_pairs(int WM, int TM, bool UP2 = false) { return TM == 1 && WM % 2 == 0 && !UP2; }
+// [r06] OW == 16 / OW == 8: a wave's 32-row block is two / four WHOLE image rows (OH * OW a multiple of 32, so a block
+// never straddles frames and starts at an even row) -- the wave pools its own slab, no partner needed: any TM == 1 tiling.
+constexpr bool tile_pools_in_wave(int TM, bool UP2 = false) { return TM == 1 && !UP2; }
+constexpr bool tile_pools_for(const GemmTile& t, int OW) { return OW == 32 ? tile_pools_in_pairs(t.wm, t.tm) : tile_pools_in_wave(t.tm); }
+// the fused up-sampling epilogue: six 32 x 32 accumulators per wave would spill beside it (the wide tiling holds them in halves)
+constexpr bool tile_has_up2(const GemmTile& t) { return t.wide || t.tm * t.tn < 6; }
+// the wide tiling: with fewer than three parts its fixed half-tile choreography has nothing left to hide the operand traffic
+// under, and it is not built for the extended scope
+constexpr bool tile_has_parts(const GemmTile& t, int P, bool ext) { return !t.wide || (P == 3 && !ext); }
+// extended scope: the BN prologue exists on the pipelined loop (per-wave tiles of 32 rows) only ...
+constexpr bool tile_has_ext_prologue(const GemmTile& t) { return t.tm == 1; }
+// ... and three stages of the 256-row tiles leave no room for the largest tables
+constexpr bool tile_ext_fits(const GemmTile& t, int P, bool PRE) {
+  return gemm_split_lds(P, t.wm, t.wn, t.tm, t.tn, t.ns, PRE, 0).limit <= kMaxLds;
+}
+
+// f(std::integral_constant<int, cfg>{}) for cfg in [0, N): kGemmTiles[cfg] is a constant expression inside f.  DH_EINVAL
+// for a cfg that is no tiling.
+template <int... I, typename F>
+int dispatch_tile_seq(int cfg, std::integer_sequence<int, I...>, F&& f) {
+  int rc = DH_EINVAL;
+  (void)((cfg == I && (rc = f(std::integral_constant<int, I>{}), true)) || ...);
+  return rc;
+}
+template <int N, typename F>
+int dispatch_tile(int cfg, F&& f) {
+  return dispatch_tile_seq(cfg, std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
 }  // namespace dh

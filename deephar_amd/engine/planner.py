@@ -54,7 +54,8 @@ from .. import graph as G
 from .rules import RuleSet
 
 # dh_softargmax2d_context_f32 (rule R5b) stages an H x W map, 16 channel lanes wide, and the two coordinate grids in LDS;
-# launch_softargmax2d_context (csrc/decoder.hip) refuses a slab above this many bytes
+# the library (csrc/decoder.hip: sam_route, exported as dh_softargmax2d_route) refuses a slab above this many bytes.  Stated here
+# as well because the planner plans without the library; tests/test_slab_ops_host.py sweeps the two against each other
 SAM_CTX_MAX_SLAB = 128 * 1024
 
 

@@ -177,6 +177,35 @@ int dh_conv2d_split_wide_eligible(const dh_conv_args* a);
  * tile_cfg in [0, dh_conv2d_num_halo_tile_cfgs()) or < 0. */
 int dh_conv2d_halo_eligible(const dh_conv_args* a);
 int dh_conv2d_num_halo_tile_cfgs(void);
+/* What dh_conv2d_f32(a, tile_cfg, .) will do, decided from the arguments alone: no pointer is dereferenced, nothing is
+ * launched.  dh_conv2d_f32 launches exactly what this says, so `rc` is its return code unless HIP itself fails
+ * (DH_ELAUNCH). */
+#define DH_CONV_GENERAL 1     /* implicit GEMM, register-staged (conv_igemm.hip): tile_cfg 0..8 */
+#define DH_CONV_DMA 2         /* LDS-DMA GEMM, fp32 (gemm1x1.hip): tile_cfg 9..17, reported as 0..8 */
+#define DH_CONV_SPLIT 3       /* LDS-DMA GEMM, split-bf16 (w_split 1 / 3 / 4, and the layers of 5 / 6 / 7 that rule accepts) */
+#define DH_CONV_SPLIT_EXT 4   /* the two layer classes the extended scope adds (w_split 5 / 6 / 7) */
+#define DH_CONV_HALO 5        /* halo-resident K x K (w_split 2) */
+#define DH_CONV_SKINNY 6      /* dh_conv2d_uses_split_k */
+#define DH_CONV_FIRST_LAYER 7 /* dh_conv2d_uses_first_layer_kernel */
+typedef struct dh_conv_route {
+  int32_t rc;       /* DH_OK, or the DH_EINVAL / DH_EUNSUPPORTED dh_conv2d_f32 answers: every other field is 0, tile_cfg -1 */
+  int32_t kernel;   /* DH_CONV_* */
+  int32_t tile_cfg; /* the tiling inside that family after the heuristic (tile_cfg < 0) and every remap: the pooled-output
+                       pick, 128 x 192 -> 128 x 96 under fused up-sampling, the halo kernel's widest TN that fits; -1 for the
+                       skinny-conv and the first-layer kernel, which have none */
+  int32_t parts;    /* bf16 parts per operand (DH_CONV_SPLIT, DH_CONV_SPLIT_EXT), else 0 */
+  int32_t bm, bn;   /* output pixels x output channels of a work-group's tile (0 x 0: first-layer kernel) */
+  int32_t tm;       /* 32-row blocks per wave: 1 = the tilings that prefetch a residual tile and may store direct; 0: no MFMA tile */
+  int32_t vec4;     /* 16-byte loads of x: the float4 gather of DH_CONV_GENERAL / DH_CONV_SKINNY (0: dword loads, same bits);
+                       always 1 for the LDS-DMA and halo kernels, 0 for the first layer */
+  int32_t epi;      /* bit 0: the 16-byte epilogue (0: scalar, as soon as one of y / res1 / res2 / the BN tables is
+                       misaligned or Cout % 4 != 0); bit 1: interior tiles store straight from the accumulators -- set for
+                       DH_CONV_DMA and DH_CONV_HALO only (halo: not with a second residual), used by tilings with tm == 1 */
+  int32_t pool;     /* y_pool: 1 = pairs of waves pool two image rows (OW = 32), 2 = a wave pools its own rows; 0: no y_pool */
+  uint32_t tiles;   /* work-groups of the launch */
+} dh_conv_route;
+/* DH_EINVAL only for a NULL argument; every other answer, refusals included, is in out->rc. */
+int dh_conv2d_route(const dh_conv_args* a, int tile_cfg, dh_conv_route* out);
 int dh_conv2d_f32(const dh_conv_args* a, int tile_cfg, void* stream);
 
 /* Stand-alone version of the same normalisation for inputs that do not feed a convolution directly:
@@ -397,6 +426,18 @@ int dh_softargmax2d_f32(const dh_sam_args* a, void* stream);
  * 40 x 48 maps fit, 44 x 48 and 40 x 52 do not) are DH_EUNSUPPORTED as well, nothing is launched. */
 int dh_softargmax2d_context_f32(const dh_sam_args* a, int J, int nctx, float agg_alpha, float* y, int ldy,
                                 void* stream);
+/* What the two launches above will do, decided from the arguments alone (nothing is dereferenced or launched; both
+ * launchers run exactly this). */
+typedef struct dh_sam_route {
+  int32_t rc;       /* dh_softargmax2d_f32(a): DH_OK or DH_EINVAL */
+  int32_t channels; /* ... channels per work-group: 16 once F * ceil(C / 16) >= 1024 work-groups fill the chip, else 4 */
+  int32_t staged;   /* ... 1: a work-group's maps are staged in LDS ((H * W * channels + W + H) * 4 bytes, at most 128 KiB
+                       with 16 channels, 60 KiB with 4); 0: read from memory twice */
+  int32_t ctx_rc;   /* dh_softargmax2d_context_f32(a, J, nctx, ., y, ldy) with a valid y and ldy >= 2: DH_OK, DH_EINVAL or
+                       DH_EUNSUPPORTED (J, nctx are not looked at for the first three fields) */
+} dh_sam_route;
+/* DH_EINVAL only for a NULL argument. */
+int dh_softargmax2d_route(const dh_sam_args* a, int J, int nctx, dh_sam_route* out);
 
 /* blocks.build_context_aggregation (blocks.py:217-285); ys [F,J,2], yc [F,J*nctx,2], pc [F,J*nctx] */
 int dh_context_aggregation_f32(const float* ys, const float* yc, const float* pc, float* y, int F, int J,

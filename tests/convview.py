@@ -5,8 +5,9 @@ tests/test_gpu_conv_views.py (GPU) and tests/test_conv_views_host.py (CPU) share
   * the case tables: every dh_conv2d_f32 case as a `Case` (geometry, operands, weight packing, the tilings to force);
   * `fill_args`: a dh_conv_args from a case, one (pointer, pitch) per operand and the table pointers -- real device pointers on
     the GPU, fake ones of the intended alignment in the host test;
-  * the launcher's rules that are not exported, restated: `vec4`, `epi` (launch_conv_igemm), the `direct` bit
-    (epi_with_direct) and `direct_tile`'s interior condition, with the statements they restate (SOURCE_STATEMENTS);
+  * `route` / `paths`: what the library says a launch will be (dh_conv2d_route: family, tiling, A gather, epilogue bits, pool
+    form) and, per output tile, the epilogue path it takes -- `direct_tile`'s interior condition is kernel-side geometry and is
+    the one thing restated here;
   * `refusal`: the launches that must answer DH_EUNSUPPORTED, and nothing else may;
   * `launch`: build the views (slabview.slab / out_slab), fill the struct, launch, synchronise, check the canaries of every
     output slab, return the views' values.
@@ -26,8 +27,8 @@ LOUD = 2.0 ** 100
 DH_EUNSUPPORTED = -2
 OPERANDS = ('x', 'y', 'res1', 'res2', 'y_pool')        # operand number k of slabview.layout: no two share a pitch or offset
 NUM_GENERAL = 9                                        # tile_cfg 0..8: implicit-GEMM kernel; 9..17: the same tiles on the LDS-DMA GEMM
-TILES = ((2, 2, 2, 3), (2, 2, 2, 2), (4, 1, 1, 3), (4, 1, 1, 2), (4, 1, 1, 1), (2, 1, 1, 3), (2, 1, 1, 2), (2, 1, 1, 1),
-         (1, 1, 1, 1))                                 # (WM, WN, TM, TN) of conv_igemm.hip: kCfgs / gemm1x1.hip: launch_gemm1x1
+# dh_conv_route.kernel -> Case.family_of (the extended scope's kernels are a split family too)
+FAMILY_OF_KERNEL = {1: 'general', 2: 'dma', 3: 'split', 4: 'split', 5: 'halo', 6: 'skinny', 7: 'stem'}
 
 
 def same_pad(size, k, s):
@@ -86,13 +87,6 @@ class Case:
             return self.family
         return 'auto' if cfg < 0 else ('general' if cfg < NUM_GENERAL else 'dma')
 
-    def tile(self, cfg):
-        """(BM, BN, TM) of a forced tiling."""
-        if self.family == 'halo':
-            return 128, 32 * (cfg + 1), 1
-        wm, wn, tm, tn = TILES[cfg % NUM_GENERAL]
-        return wm * tm * 32, wn * tn * 32, tm
-
     def __repr__(self):
         return self.name
 
@@ -143,6 +137,12 @@ def refusal(case, lay, tables_unaligned, cfg):
     return None
 
 
+def refused_by_shape(case, cfg):
+    """The launches of the tables the library refuses on EVERY layout, as test_gpu_conv_views.test_conv2d_on_views states them:
+    the 13 x 11 split cases (a skinny layer by the shape rule) and the wide tilings 14 and 15 below three parts."""
+    return case.family == 'split' and ('13x11' in case.name or (cfg in (14, 15) and case.w_split != 1))
+
+
 def fill_args(case, ptr, ld, w=16, tables=None, in_lut=None):
     """dh_conv_args of `case`: ptr / ld map an operand to its view's pointer / pixel pitch, tables maps 'pre_scale' .. to
     pointers.  No pointer is dereferenced here."""
@@ -177,32 +177,11 @@ def fake_args(case, lay, tables_unaligned):
     return fill_args(case, ptr, ld, 0x8000000, tab, in_lut=0x9000000 if case.x_u8 else None)
 
 
-# ---- the launcher's unexported rules, restated ------------------------------------------------------------------------------
-def _al16(p):
-    return (p or 0) % 16 == 0
-
-
-def epi(a):
-    """launch_conv_igemm: 1 = the 16-byte epilogue; 0 as soon as ONE of y, res1, res2 or the BN tables is misaligned."""
-    return int(a.Cout % 4 == 0 and a.ldy % 4 == 0 and _al16(a.y) and
-               (not a.res1 or (a.ldr1 % 4 == 0 and _al16(a.res1))) and
-               (not a.res2 or (a.ldr2 % 4 == 0 and _al16(a.res2))) and
-               (not a.post_scale or (_al16(a.post_scale) and _al16(a.post_shift))))
-
-
-def vec4(a):
-    """launch_conv_igemm: the float4 A gather of the general kernel."""
-    return int(not a.x_u8 and a.Cin % 4 == 0 and a.ldx % 4 == 0 and _al16(a.x) and
-               (not a.pre_scale or ((a.pre_scale | (a.pre_shift or 0)) & 15) == 0))
-
-
-def direct_bit(a, e, half_res_residual=True):
-    """epi_with_direct: interior tiles may store straight from the accumulators."""
-    M, ohw = a.N * a.OH * a.OW, a.OH * a.OW
-    r2ok = not a.res2 or bool(half_res_residual and a.res2_down and (a.OW & (a.OW - 1)) == 0 and (ohw & (ohw - 1)) == 0 and
-                              a.OW >= 8 and ohw >= 32 and (M // 4) * a.ldr2 * 4 < 0x7fffffff)
-    return bool(e and not a.up2 and not a.y_pool and r2ok and M * a.ldy * 4 < 0x7fffffff and
-                (not a.res1 or M * a.ldr1 * 4 < 0x7fffffff))
+# ---- what the library says a launch will be ------------------------------------------------------------------------------------
+def route(lib, a, cfg):
+    """dh_conv2d_route(a, cfg) as a ctypes struct: rc, kernel, tile_cfg, parts, bm, bn, tm, vec4, epi, pool, tiles."""
+    from deephar_amd import _lib
+    return _lib.conv_route(lib, a, cfg)
 
 
 def direct_tile(m0, n0, bm, bn, M, cout):
@@ -210,55 +189,31 @@ def direct_tile(m0, n0, bm, bn, M, cout):
     return m0 + bm <= M and n0 + bn <= cout
 
 
-# (file, statement): each must stand ONCE in the source as written (white space aside)
-SOURCE_STATEMENTS = (
-    ('conv_igemm.hip', 'const int epi = (a.Cout % 4 == 0) && (a.ldy % 4 == 0) && al16(a.y) && '
-                       '(a.res1 == nullptr || (a.ldr1 % 4 == 0 && al16(a.res1))) && '
-                       '(a.res2 == nullptr || (a.ldr2 % 4 == 0 && al16(a.res2))) && '
-                       '(a.post_scale == nullptr || (al16(a.post_scale) && al16(a.post_shift)));'),
-    ('conv_igemm.hip', 'const bool vec4 = !a.x_u8 && (a.Cin % 4 == 0) && (a.ldx % 4 == 0) && '
-                       '((reinterpret_cast<uintptr_t>(a.x) & 15) == 0) && (a.pre_scale == nullptr || '
-                       '(((reinterpret_cast<uintptr_t>(a.pre_scale) | reinterpret_cast<uintptr_t>(a.pre_shift)) & 15) == 0));'),
-    ('conv_igemm.hip', 'if (a.y_pool != nullptr && !epi) return DH_EUNSUPPORTED;'),
-    ('conv_igemm.hip', 'return launch_gemm1x1(a, cfg, epi_with_direct(a, epi), s);'),
-    ('conv_igemm.hip', 'if (a.w_split == 2) return launch_conv_halo(a, cfg, epi_with_direct(a, epi, false), s);'),
-    ('conv_igemm.hip', 'return launch_gemm1x1_split(a, cfg, epi, s);'),
-    ('conv_igemm.hip', 'conv_epilogue<WM, WN, TM, TN, UP2, false>(p, acc, smem, m0, n0, M, epi_vec, pre);'),
-    ('conv_common.h', 'const bool r2ok = a.res2 == nullptr || (half_res_residual && a.res2_down && (a.OW & (a.OW - 1)) == 0 && '
-                      '(ohw & (ohw - 1)) == 0 && a.OW >= 8 && ohw >= 32 && (M / 4) * a.ldr2 * 4 < 0x7fffffffLL);'),
-    ('conv_common.h', 'const bool direct = epi && !a.up2 && a.y_pool == nullptr && r2ok && M * a.ldy * 4 < 0x7fffffffLL && '
-                      '(a.res1 == nullptr || M * a.ldr1 * 4 < 0x7fffffffLL);'),
-    ('conv_common.h', 'return (epi_vec & 2) != 0 && m0 + WM * TM * 32 <= M && n0 + WN * TN * 32 <= p.Cout;'),
-    ('conv_common.h', 'static constexpr bool kEnabled = (TM == 1);'),
-    ('conv_common.h', 'const bool pow2 = (p.OW & (p.OW - 1)) == 0 && (ohw & (ohw - 1)) == 0;'),
-)
-
-
-def paths(case, a, cfg):
+def paths(lib, case, a, cfg):
     """What a launch that runs (a forced tiling of the general kernel, the DMA GEMM or the halo kernel) goes through:
     'vec4' / 'scalar_a' (general kernel), per output tile 'direct' / 'staged_vec' / 'staged_scalar', the form of a
     half-resolution second residual and of the pooled second output."""
-    fam = case.family_of(cfg)
-    assert fam in ('general', 'dma', 'halo', 'split') and cfg >= 0, (case, cfg)
+    r = route(lib, a, cfg)
+    fam = FAMILY_OF_KERNEL.get(r.kernel)
+    assert r.rc == 0 and fam == case.family_of(cfg) and fam in ('general', 'dma', 'halo', 'split') and cfg >= 0, (case, cfg, r.rc, fam)
     out = set()
     if fam == 'general':
-        out.add('vec4' if vec4(a) else 'scalar_a')
-    e = epi(a)
-    bm, bn, tm = case.tile(cfg)
-    # the direct path needs a prefetched residual tile (TM == 1) in a kernel that calls the epilogue with PRE: the fp32 DMA
-    # GEMM and the halo kernel (no half-resolution residual there); the general kernel and the split GEMM pass plain `epi`
-    d = fam in ('dma', 'halo') and tm == 1 and direct_bit(a, e, fam != 'halo')
+        out.add('vec4' if r.vec4 else 'scalar_a')
+    e = r.epi & 1
+    # the direct path needs the launcher's bit (the fp32 DMA GEMM, and the halo kernel without a second residual; the general
+    # kernel and the split GEMM get plain `epi`) and a tiling that prefetches a residual tile (tm == 1)
+    d = bool(r.epi & 2) and r.tm == 1
     ohw = a.OH * a.OW
     pow2 = (a.OW & (a.OW - 1)) == 0 and (ohw & (ohw - 1)) == 0
-    for m0 in range(0, case.M, bm):
-        for n0 in range(0, a.Cout, bn):
-            kind = 'direct' if d and direct_tile(m0, n0, bm, bn, case.M, a.Cout) else ('staged_vec' if e else 'staged_scalar')
+    for m0 in range(0, case.M, r.bm):
+        for n0 in range(0, a.Cout, r.bn):
+            kind = 'direct' if d and direct_tile(m0, n0, r.bm, r.bn, case.M, a.Cout) else ('staged_vec' if e else 'staged_scalar')
             out.add(kind)
             if a.res2_down:
                 out.add('down_direct' if kind == 'direct' else
                         ('down_staged_pow2' if pow2 else 'down_staged_div') if kind == 'staged_vec' else 'down_scalar')
-    if a.y_pool:
-        out.add('pool_pair' if a.OW == 32 else 'pool_in_wave')
+    if r.pool:
+        out.add('pool_pair' if r.pool == 1 else 'pool_in_wave')
     return out
 
 
@@ -408,6 +363,7 @@ def launch(lib, case, data, lay, w, cfg=-1, tables_unaligned=False, x_lead=0, wh
     a = fill_args(case, v.ptr, v.ld, wt.data_ptr(), tab, in_lut=lut)
     rc = lib.dh_conv2d_f32(C.byref(a), cfg, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
+    assert route(lib, a, cfg).rc == rc, (case, what, cfg, rc)          # the library said so before it launched
     if rc != 0:
         v.assert_nothing_written(what)
         return rc, None

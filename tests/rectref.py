@@ -57,7 +57,7 @@ def transposed(out):
 
 
 # ---- the cases the host test (discrimination) and the GPU tests share ---------------------------------------------------
-# (F, H, W, C) -> (channels per work-group, staged in LDS) of softargmax2d_kernel, as slabview.sam_variant predicts it; every
+# (F, H, W, C) -> (channels per work-group, staged in LDS) of softargmax2d_kernel, as the library answers (slabview.sam_variant); every
 # shape comes with its transpose
 SAM_SHAPES = {
     (3, 12, 20, 17): (4, True), (3, 20, 12, 17): (4, True),

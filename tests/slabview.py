@@ -16,7 +16,8 @@ Three layouts are used throughout (`layout`):
 `k` = 0, 1, 2 .. gives the operands of one launch different pitches and offsets.
 
 Also here, because the GPU test and the host test share it: the shapes that reach the four instantiations of the 2-D
-soft-argmax kernel, and the launcher's variant choice restated (`sam_variant`).
+soft-argmax kernel, and what the library says it will launch for a shape (`sam_variant`, `sam_ctx_rc`: dh_softargmax2d_route
+on fake pointers -- nothing of the launchers is restated).
 """
 import numpy as np
 
@@ -85,27 +86,32 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-# ---- the 2-D soft-argmax launcher's variant choice (csrc/decoder.hip: launch_softargmax2d), restated ------------------
-SAM_WIDE_BLOCKS = 1024             # `blocks16 >= 1024`: 16 channels per work-group once F * ceil(C / 16) fills the chip
-SAM_SLAB_WIDE = 128 * 1024         # bytes of LDS above which the 16-channel kernel reads the maps from memory
-SAM_SLAB_NARROW = 60 * 1024        # the same for the 4-channel kernel
-SAM_CTX_SLAB = 128 * 1024          # launch_softargmax2d_context: bytes of LDS (16 channel lanes) above which it REFUSES the launch
-# the statements of the launchers the four numbers restate, as they stand in the source
-SAM_SOURCE_LINES = ('const bool wide = blocks16 >= 1024;',
-                    'constexpr size_t kMaxSlab = 128 * 1024;',
-                    'if (slab > (wide ? kMaxSlab : (size_t)60 * 1024)) {',
-                    'if (slab > 128 * 1024) return DH_EUNSUPPORTED;')
-
-
+# ---- the 2-D read-outs' launch decision, asked of the library (dh_softargmax2d_route) ------------------------------------------
 def sam_slab_bytes(H, W, g):
+    """LDS bytes of g channels of an H x W map and the two grids (include/deephar_hip.h: dh_sam_route.staged)."""
     return (H * W * g + W + H) * 4
 
 
-def sam_variant(F, H, W, C):
+def sam_route(lib, F, H, W, C, J=0, nctx=0, ldh=None, h=0x100000):
+    """dh_softargmax2d_route for an [F, H, W, C] launch on fake, 16-byte aligned pointers; only conf_raw of the optional
+    outputs is asked for, as the fused read-out requires."""
+    from deephar_amd import _lib
+    a = _lib.SamArgs()
+    a.h, a.gx, a.gy, a.conf_raw = h, 0x200000, 0x300000, 0x400000
+    a.F, a.H, a.W, a.C, a.ldh, a.ldxy, a.ldcr, a.ldcp, a.ldp = F, H, W, C, ldh or C, 2, 1, 1, C
+    return _lib.sam_route(lib, a, J, nctx)
+
+
+def sam_variant(lib, F, H, W, C):
     """(channels per work-group, staged in LDS) of softargmax2d_kernel<G, STAGED> for an [F, H, W, C] launch."""
-    wide = F * ((C + 15) // 16) >= SAM_WIDE_BLOCKS
-    g = 16 if wide else 4
-    return g, sam_slab_bytes(H, W, g) <= (SAM_SLAB_WIDE if wide else SAM_SLAB_NARROW)
+    r = sam_route(lib, F, H, W, C)
+    assert r.rc == 0, (F, H, W, C, r.rc)
+    return r.channels, bool(r.staged)
+
+
+def sam_ctx_rc(lib, H, W, J=8, nctx=2, F=2):
+    """The code dh_softargmax2d_context_f32 answers for J joints with nctx context maps each on H x W maps (0: it launches)."""
+    return sam_route(lib, F, H, W, J * (1 + nctx), J, nctx).ctx_rc
 
 
 # (F, H, W, C) -> the instantiation the shape is there for

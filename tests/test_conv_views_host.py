@@ -1,7 +1,7 @@
-"""Host tests (no GPU) that go with tests/test_gpu_conv_views.py: every case of tests/convview.py reaches the kernel family it
-is there for, by the library's own exported rules on fake pointers of the intended alignment; the launcher's unexported
-predicates (vec4, epi, the direct bit, direct_tile) are restated in convview and the statements they restate still stand in
-the source; the case tables reach every form of the A load, the epilogue, the half-resolution residual and the pooled output."""
+"""Host tests (no GPU) that go with tests/test_gpu_conv_views.py, on fake pointers of the intended alignment and by the library's
+own answers (dh_conv2d_route and the exported rules; nothing of the launcher is restated): every case of tests/convview.py
+reaches the kernel family it is there for, every launch of the tables is refused exactly where convview.refusal says, and
+the case tables reach every form of the A load, the epilogue, the half-resolution residual and the pooled output."""
 import ctypes as C
 import os
 import re
@@ -29,9 +29,22 @@ def _dma_shape(hip_lib, case, a):
 
 
 def test_every_case_reaches_its_family(hip_lib):
-    seen = set()
+    seen, calls = set(), {0: 0, CV.DH_EUNSUPPORTED: 0}
     for case, sname, lay, tabs, a in _launches():
         what = (case.name, sname)
+        for cfg in case.cfgs:
+            # the refusal table, asked of the library: DH_EUNSUPPORTED for every listed refusal, and a route of the case's family
+            # for everything else.  The exceptions are those of test_gpu_conv_views.test_conv2d_on_views: the 13 x 11 split
+            # cases (a skinny layer by the shape rule: refused on every layout) and the wide tilings below three parts
+            r = CV.route(hip_lib, a, cfg)
+            want = CV.DH_EUNSUPPORTED if CV.refused_by_shape(case, cfg) or CV.refusal(case, lay, tabs, cfg) else 0
+            assert r.rc == want, (what, cfg, r.rc)
+            calls[r.rc] += 1
+            if r.rc == 0:
+                fam = case.family_of(cfg)
+                if fam == 'auto':                            # the library's own pick: the DMA GEMM unless x is misaligned
+                    fam = 'general' if lay['x'] == 'odd' else 'dma'
+                assert CV.FAMILY_OF_KERNEL[r.kernel] == fam, (what, cfg, r.kernel)
         skinny = hip_lib.dh_conv2d_uses_split_k(C.byref(a))
         stem = hip_lib.dh_conv2d_uses_first_layer_kernel(C.byref(a))
         x_ok = int(lay['x'] != 'odd')
@@ -54,6 +67,7 @@ def test_every_case_reaches_its_family(hip_lib):
             if any(c < 0 or c >= CV.NUM_GENERAL for c in case.cfgs):
                 assert _dma_shape(hip_lib, case, a) == x_ok, what
     assert seen == {'fp32', 'halo', 'split', 'skinny', 'stem'}
+    assert calls == {0: 1214, CV.DH_EUNSUPPORTED: 672}, calls              # 1886 launches of the tables
     # the shape (c) / (i) name for K x K on the DMA GEMM: 143 positions, K = 576, 72 channels -- a skinny layer
     from deephar_amd.engine.planner import split_k_rule
     assert split_k_rule(13 * 11, 576, 72, 64) and not split_k_rule(35 * 33, 576, 72, 64) and not split_k_rule(18 * 17, 576, 72, 64)
@@ -72,21 +86,6 @@ def test_transposed_conv_cases_are_eligible_on_an_aligned_x_only(hip_lib):
             assert off > 0 and hip_lib.dh_conv2d_transpose2x2_split_eligible(C.byref(a)) == want, (cout, name)
 
 
-def test_launcher_rules_restated_still_stand_in_the_source():
-    src = {}
-    for fname, stmt in CV.SOURCE_STATEMENTS:
-        if fname not in src:
-            src[fname] = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'deephar_amd', 'csrc', fname)).read())
-        assert src[fname].count(re.sub(r'\s+', ' ', stmt)) == 1, \
-            '%s no longer says `%s` once: restate it in tests/convview.py' % (fname, stmt)
-    assert CV.TILES == ((2, 2, 2, 3), (2, 2, 2, 2), (4, 1, 1, 3), (4, 1, 1, 2), (4, 1, 1, 1), (2, 1, 1, 3), (2, 1, 1, 2),
-                        (2, 1, 1, 1), (1, 1, 1, 1))
-    for i, (wm, wn, tm, tn) in enumerate(CV.TILES):         # the same nine tiles in both fp32 families
-        assert src['conv_igemm.hip'].count('case %d: return launch_cfg<%d, %d, %d, %d>(a, vec4, epi, s);' % (i, wm, wn, tm, tn)) == 1
-        gsrc = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'deephar_amd', 'csrc', 'gemm1x1.hip')).read())
-        assert gsrc.count('case %d: return launch_cfg<%d, %d, %d, %d>(a, epi, s);' % (i, wm, wn, tm, tn)) == 1
-
-
 def test_no_source_includes_a_source_and_the_split_tilings_stand_once():
     """The kernel sources share code through headers only, and the split-bf16 tilings -- stated once, in gemm_family.h, for the
     standard and the extended scope -- are the ones the benchmark names its kernels by."""
@@ -97,34 +96,54 @@ def test_no_source_includes_a_source_and_the_split_tilings_stand_once():
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     import bench
-    tiles = {int(c): (tuple(int(v) for v in t.split(',')[:4]), int((t.split(',') + ['2'])[4]))
-             for c, t in re.findall(r'case (\d+): return f\(SplitTile<([\d, ]+)>\{\}\);', texts['gemm_family.h'])}
-    wide = {int(c): int(wm) for c, wm in re.findall(r'case (\d+): return f\(SplitWideTile<(\d+)>\{\}\);', texts['gemm_family.h'])}
+    # a row of kGemmTiles: `{wm, wn, tm, tn, ns},  // cfg: ...`; the wide tilings end in `true` and spell their 192 columns as tn = 6
+    row = r'\{(\d+), (\d+), (\d+), (\d+), (\d+)(, true)?\},\s*//\s*(\d+):'
+    found = re.findall(row, texts['gemm_family.h'])
+    tiles = {int(c): (tuple(int(v) for v in t[:4]), int(t[4])) for *t, w, c in found if not w}
+    wide = {int(c): int(t[0]) for *t, w, c in found if w}
+    assert all(tuple(t[1:]) == ('1', '1', '6', '2') for *t, w, c in found if w)
     assert tiles == bench.SPLIT_TILES and wide == bench.SPLIT_WIDE
-    assert sorted(tiles) + sorted(wide) == list(range(16))
-    rows = [(f, m) for f, text in texts.items() for m in re.findall(r'Split(?:Wide)?Tile<[\d, ]+>', text)]
-    assert len(rows) == 16 and all(f == 'gemm_family.h' for f, _ in rows), rows     # nowhere else, and none twice
+    assert sorted(tiles) + sorted(wide) == list(range(16)) and [int(c) for *_, c in found] == list(range(16))
+    # nowhere else, and none twice: no other table row, and no tiling spelled out as template arguments of a launch
+    rows = [(f, m) for f, text in texts.items() for m in re.findall(row, text)]
+    assert len(rows) == 16 and all(f == 'gemm_family.h' for f, _ in rows), rows
+    spelled = [(f, m) for f, text in texts.items() for m in re.findall(r'(?:launch_cfg|launch_ext_cfg|Tile)<[\d, ]+>', text)]
+    assert not spelled, spelled
 
 
-def test_case_tables_reach_every_path_of_the_launcher():
+def _epi_and_gather(hip_lib, case, a):
+    """(16-byte epilogue, float4 A gather) of a struct as the library's routes say: over the case's tilings and, for the fp32
+    family, the general kernel's 128 x 64 (the only kernel with a scalar gather).  Each is the one value all accepted routes
+    agree on, None where no kernel with that choice accepts the struct."""
+    cfgs = set(case.cfgs) | ({3} if case.family == 'fp32' else set())
+    routes = [r for r in (CV.route(hip_lib, a, c) for c in sorted(cfgs)) if r.rc == 0]
+    es = {r.epi & 1 for r in routes if CV.FAMILY_OF_KERNEL[r.kernel] in ('general', 'dma', 'split', 'halo')}
+    vs = {r.vec4 for r in routes if CV.FAMILY_OF_KERNEL[r.kernel] == 'general'}
+    assert len(es) <= 1 and len(vs) <= 1, (case.name, es, vs)
+    return (es.pop() if es else None), (vs.pop() if vs else None)
+
+
+def test_case_tables_reach_every_path_of_the_launcher(hip_lib):
     reached, per = set(), {}
     for case, sname, lay, tabs, a in _launches():
-        e, v = CV.epi(a), CV.vec4(a)
+        e, v = _epi_and_gather(hip_lib, case, a)
+        if case.family == 'fp32' and not case.up2 and not (case.pool and CV.refusal(case, lay, tabs, 3)):
+            assert e is not None and v is not None, (case.name, sname)        # (the general kernel takes every layout)
         # a single misaligned operand is enough to send the whole epilogue / the whole gather scalar
         if sname in ('odd_y', 'odd_res1', 'odd_res2') or (sname == 'tables' and case.bn):
-            assert e == 0, (case.name, sname)
+            assert e in (0, None), (case.name, sname)
         if sname == 'odd_x' or (sname == 'tables' and case.pre_bn):
-            assert v == 0, (case.name, sname)
+            assert v in (0, None), (case.name, sname)
         if sname in ('dense', 'aligned') and case.Cout % 4 == 0:
-            assert e == 1 and (v == 1 or case.Cin % 4 != 0 or case.x_u8), (case.name, sname)
+            assert e in (1, None) and (v in (1, None) or case.Cin % 4 != 0 or case.x_u8), (case.name, sname)
         if sname == 'odd_y_pool':
             assert all(CV.refusal(case, lay, tabs, c) for c in case.cfgs), case.name
         if case.family not in ('fp32', 'halo', 'split'):
             continue
         for cfg in case.cfgs:
-            if cfg < 0 or CV.refusal(case, lay, tabs, cfg):
+            if cfg < 0 or CV.refusal(case, lay, tabs, cfg) or CV.refused_by_shape(case, cfg):
                 continue
-            p = CV.paths(case, a, cfg)
+            p = CV.paths(hip_lib, case, a, cfg)
             per[(case.name, sname, cfg)] = p
             reached |= p
     assert reached >= {'vec4', 'scalar_a', 'staged_vec', 'staged_scalar', 'direct', 'down_direct', 'down_staged_div',
@@ -135,7 +154,8 @@ def test_case_tables_reach_every_path_of_the_launcher():
             assert per[(name, 'aligned', cfg)] == {'vec4', 'staged_vec'} and per[(name, 'odd', cfg)] == {'scalar_a', 'staged_scalar'}
     # (b) tile_cfg 12: direct on the 6 x 3 interior tiles, staged on the ragged ones; 10 (TM = 2) has no prefetch: staged
     c = CV.CASES['b_dma']
-    assert c.tile(12) == (128, 64, 1) and c.M // 128 == 6 and c.Cout // 64 == 3 and c.M % 128 and c.Cout % 64
+    r = CV.route(hip_lib, CV.fake_args(c, *CV.layout_sets(c)['aligned']), 12)
+    assert (r.bm, r.bn, r.tm) == (128, 64, 1) and c.M // 128 == 6 and c.Cout // 64 == 3 and c.M % 128 and c.Cout % 64
     assert per[('b_dma', 'aligned', 12)] == {'direct', 'staged_vec'} and per[('b_dma', 'aligned', 10)] == {'staged_vec'}
     assert per[('b_dma', 'odd_res1', 12)] == {'staged_scalar'} and per[('b_dma', 'tables', 12)] == {'staged_scalar'}
     # (e) the power-of-two direct form on every tile | the staged form with integer divides

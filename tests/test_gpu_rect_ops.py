@@ -70,10 +70,10 @@ def _sam_run(h, alpha, cuda):
 @pytest.mark.parametrize('alpha', R.SAM_ALPHAS)
 @pytest.mark.parametrize('shape', sorted(R.SAM_SHAPES), ids=_ids)
 def test_softargmax2d_on_rectangular_maps(shape, alpha, hip_lib, cuda):
-    """All four instantiations of softargmax2d_kernel (the shape rule of slabview predicts which: asserted) and the grid copy
+    """All four instantiations of softargmax2d_kernel (the library says which: asserted) and the grid copy
     loops beyond the 256 threads, on H != W: the assertions and bars of test_gpu_ops.test_softargmax2d against oracle/ops.py,
     and the same bars against rectref's fp64 values."""
-    assert SV.sam_variant(*shape) == R.SAM_SHAPES[shape]
+    assert SV.sam_variant(hip_lib, *shape) == R.SAM_SHAPES[shape]
     r = _sam_ref(shape, alpha)
     out = _sam_run(r['h'], alpha, cuda)
     what = 'softargmax2d %s alpha %g' % (shape, alpha)
@@ -100,7 +100,7 @@ def test_softargmax2d_of_the_transposed_maps(shape, hip_lib, cuda):
     h = R.sam_input(shape)
     a = _sam_run(h, 1.0, cuda)
     b = _sam_run(np.swapaxes(h, 1, 2), 1.0, cuda)
-    assert SV.sam_variant(shape[0], shape[2], shape[1], shape[3]) == R.SAM_SHAPES[shape]        # (same instantiation)
+    assert SV.sam_variant(hip_lib, shape[0], shape[2], shape[1], shape[3]) == R.SAM_SHAPES[shape]        # (same instantiation)
     d = np.abs(a['xy'][..., ::-1] - b['xy']).max()
     print('transposed %s: xy %.3e' % (shape, d))
     assert d <= BAR
@@ -203,7 +203,7 @@ def test_softargmax2d_context_on_rectangular_maps(shape, joints, nctx, hip_lib, 
     plain kernel."""
     from deephar_amd import functional as F
     f, hh, ww, ld = shape
-    assert SV.sam_slab_bytes(hh, ww, 16) <= SV.SAM_CTX_SLAB
+    assert SV.sam_ctx_rc(hip_lib, hh, ww, joints, nctx, f) == 0
     rng = np.random.default_rng(sum(shape) + nctx)
     h = OPS._rand(rng, shape, 4.0) + 1.0                     # (positive offset: context confidences away from 0)
     t = torch.from_numpy(h)
@@ -235,7 +235,7 @@ def test_softargmax2d_context_refuses_maps_beyond_its_lds_slab(shape, hip_lib, c
     aggregation: tests/test_rect_host.py.)"""
     f, hh, ww, ch = shape
     j, nctx = 16, 2
-    assert SV.sam_slab_bytes(hh, ww, 16) > SV.SAM_CTX_SLAB
+    assert SV.sam_ctx_rc(hip_lib, hh, ww, j, nctx, f) == DH_EUNSUPPORTED
     x = SLAB._In(np.ones(shape, np.float32), ch, 0)
     y, conf = SLAB._Out((f, j, 2), 2, 0), SLAB._Out((f, j, 1), 1, 0)
     gx = SLAB._dev(np.linspace(0.0, 1.0, num=ww).astype(np.float32), cuda)

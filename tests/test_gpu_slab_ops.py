@@ -350,8 +350,8 @@ def _sam_check(out, r, what):
 @pytest.mark.parametrize('shape', [s for s in SV.SAM_VARIANT_SHAPES if s != (3, 16, 16, 17)])
 def test_softargmax2d_every_instantiation(shape, hip_lib, cuda):
     """<16, true> (also with a second channel group of one live channel), <16, false> and <4, false>: the shapes of
-    slabview.SAM_VARIANT_SHAPES (tests/test_slab_ops_host.py holds them to the launcher's rule)."""
-    assert SV.sam_variant(*shape) == SV.SAM_VARIANT_SHAPES[shape]
+    slabview.SAM_VARIANT_SHAPES (tests/test_slab_ops_host.py holds them to the library's answer)."""
+    assert SV.sam_variant(hip_lib, *shape) == SV.SAM_VARIANT_SHAPES[shape]
     r = _sam_case(shape)
     out = _sam_launch(hip_lib, cuda, r['h'], shape[3], 0)
     _sam_check(out, r, 'softargmax2d %s' % (shape,))

@@ -31,6 +31,8 @@ def test_ctypes_structs_match_header_layout(hip_lib, tmp_path):
              'dh_elt_args': _lib.EltArgs, 'dh_sam_args': _lib.SamArgs}
     structs = set(re.findall(r'typedef struct (dh_\w+_args)', header))
     assert structs == set(pairs), structs ^ set(pairs)
+    pairs.update({'dh_conv_route': _lib.ConvRoute, 'dh_sam_route': _lib.SamRoute})      # the two structs the library fills
+    assert all('typedef struct %s {' % n in header for n in pairs)
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "deephar_hip.h"', 'int main(void) {']
     for cname, ct in pairs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

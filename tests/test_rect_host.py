@@ -57,25 +57,25 @@ def readout(plan):
 # ---- 1. rule R5b ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('rows,cols,fused', [(320, 384, True), (288, 448, True),
                                              (320, 416, False), (352, 384, False), (384, 384, False)])
-def test_fused_decoder_is_planned_only_inside_its_lds_limit(rows, cols, fused):
+def test_fused_decoder_is_planned_only_inside_its_lds_limit(rows, cols, fused, hip_lib):
     """1-block ReceptionNet 2-D with context.  40 x 48 and 36 x 56 maps (the largest the hourglass can be built at that fit:
     129 392 B) plan `sam_ctx`; 40 x 52, 44 x 48 and 48 x 48 maps (133 488, 135 536 and 147 840 B > 131 072) keep two `sam`
     steps and one `context_agg` -- before the planner knew the limit it planned `sam_ctx` there and Model.predict raised in
     the middle of the launch sequence."""
     H, W = rows // 8, cols // 8
-    assert (SV.sam_slab_bytes(H, W, 16) <= SV.SAM_CTX_SLAB) == fused           # the case is on the side it is meant for
+    assert (SV.sam_ctx_rc(hip_lib, H, W) == 0) == fused                        # the case is on the side it is meant for
     plan = context_model(rows, cols).plan
     assert all(s.ins['h'].shape[-3:-1] == (H, W) for s in plan.steps if s.kind in ('sam', 'sam_ctx'))
     assert readout(plan) == (['sam_ctx'] if fused else ['sam', 'sam', 'context_agg']), (H, W, readout(plan))
 
 
 @pytest.mark.parametrize('H,W,fused', [(45, 45, True), (45, 46, False), (32, 32, True), (3, 300, True), (300, 7, False)])
-def test_fused_decoder_limit_on_the_decoder_alone(H, W, fused):
+def test_fused_decoder_limit_on_the_decoder_alone(H, W, fused, hip_lib):
     """The same rule at the map sizes next to the limit, odd ones included (a 360 x 360 crop gives 45 x 45 maps: 129 960 B,
     inside; 45 x 46: 132 844 B, outside), on the decoder behind a 1x1 convolution -- reception.build cannot be built there."""
     with pytest.raises(ValueError):
         context_model(8 * 45, 8 * 45)                      # (why this test has a graph of its own)
-    assert (SV.sam_slab_bytes(H, W, 16) <= SV.SAM_CTX_SLAB) == fused
+    assert (SV.sam_ctx_rc(hip_lib, H, W) == 0) == fused
     assert readout(decoder_only(H, W).plan) == (['sam_ctx'] if fused else ['sam', 'sam', 'context_agg'])
 
 
@@ -164,12 +164,12 @@ def test_the_two_orientations_are_different_plans():
 
 # ---- 3. the op-level inputs can tell H from W ----------------------------------------------------------------------------------
 @pytest.mark.parametrize('shape', sorted(R.SAM_SHAPES), ids=lambda s: 'x'.join(map(str, s)))
-def test_sam_shapes_reach_their_instantiation_and_tell_rows_from_columns(shape):
-    """Each shape of the GPU test reaches the instantiation it is there for (slabview.sam_variant: the launcher's rule), and on
+def test_sam_shapes_reach_their_instantiation_and_tell_rows_from_columns(shape, hip_lib):
+    """Each shape of the GPU test reaches the instantiation it is there for (slabview.sam_variant: the library's answer), and on
     its random input a read-out with the roles of H and W exchanged (rectref.softargmax(swapped=True): x normalised by H - 1,
     r = px / H, the window guard with H and W exchanged) is at least 100 x the bar away from the right one, on the
     coordinates and the raw confidence at either alpha and on the soft-max confidence at alpha 1: an exchange in the kernel cannot hide inside the tolerance."""
-    assert SV.sam_variant(*shape) == R.SAM_SHAPES[shape]
+    assert SV.sam_variant(hip_lib, *shape) == R.SAM_SHAPES[shape]
     assert shape[1] != shape[2]
     h = R.sam_input(shape)
     prob_tells = []

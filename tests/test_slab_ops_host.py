@@ -1,36 +1,41 @@
 """Host tests (no GPU) that go with tests/test_gpu_slab_ops.py: the shapes its soft-argmax cases use reach all four
-instantiations of softargmax2d_kernel, by the launcher's own rule."""
+instantiations of softargmax2d_kernel, by the library's own answer (dh_softargmax2d_route)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import slabview as SV                              # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def test_softargmax2d_shapes_reach_all_four_instantiations():
+def test_softargmax2d_shapes_reach_all_four_instantiations(hip_lib):
     """launch_softargmax2d picks <16, *> when F * ceil(C / 16) >= 1024 and the un-staged kernels when the LDS slab would
-    exceed 128 KB (wide) or 60 KB (narrow).  slabview.sam_variant restates that rule; the statements it restates must still
-    stand in the source as written, so that a change of a threshold fails here and the shapes are looked at again instead
-    of quietly becoming several tests of one variant."""
-    src = open(os.path.join(ROOT, 'deephar_amd', 'csrc', 'decoder.hip')).read()
-    for line in SV.SAM_SOURCE_LINES:
-        assert src.count(line) == 1, 'launch_softargmax2d no longer says `%s`: restate slabview.sam_variant' % line
-    assert 'const size_t slab = ((size_t)a.H * a.W * g + a.W + a.H) * sizeof(float);' in src
-    # the fused read-out (rule R5b) has no unstaged variant: the planner restates its refusal (tests/test_rect_host.py)
-    from deephar_amd.engine import planner
-    assert 'const size_t slab = ((size_t)a.H * a.W * CG + a.W + a.H) * sizeof(float);' in src and 'constexpr int CG = 16;' in src
-    assert planner.SAM_CTX_MAX_SLAB == SV.SAM_CTX_SLAB
-    assert all(planner.sam_ctx_slab_bytes(h, w) == SV.sam_slab_bytes(h, w, 16) for h, w in ((45, 45), (40, 52), (3, 300)))
+    exceed 128 KB (wide) or 60 KB (narrow).  The library says which (dh_softargmax2d_route, the function the launcher runs), so
+    a change of a threshold fails here and the shapes are looked at again instead of quietly becoming several tests of one
+    variant."""
     for shape, want in SV.SAM_VARIANT_SHAPES.items():
-        assert SV.sam_variant(*shape) == want, (shape, SV.sam_variant(*shape), want)
+        assert SV.sam_variant(hip_lib, *shape) == want, (shape, SV.sam_variant(hip_lib, *shape), want)
     assert set(SV.SAM_VARIANT_SHAPES.values()) == {(16, True), (16, False), (4, True), (4, False)}
-    # the slab sizes the shapes were chosen by, and the rule at its edges
-    assert SV.sam_slab_bytes(46, 46, 16) == 135792 > SV.SAM_SLAB_WIDE
-    assert SV.sam_slab_bytes(64, 64, 4) == 66048 > SV.SAM_SLAB_NARROW
-    assert SV.sam_variant(1023, 4, 4, 16) == (4, True) and SV.sam_variant(1024, 4, 4, 16) == (16, True)
-    assert SV.sam_variant(1, 32, 32, 272) == (4, True)      # the largest shape of test_gpu_ops.test_softargmax2d: 17 groups
+    # the slab sizes the shapes were chosen by, and the rule at its edges: 128 KiB with 16 channels, 60 KiB with 4
+    assert SV.sam_slab_bytes(46, 46, 16) == 135792 > 128 * 1024 and SV.sam_variant(hip_lib, 1024, 46, 46, 3) == (16, False)
+    assert SV.sam_slab_bytes(45, 45, 16) == 129960 <= 128 * 1024 and SV.sam_variant(hip_lib, 1024, 45, 45, 3) == (16, True)
+    assert SV.sam_slab_bytes(64, 64, 4) == 66048 > 60 * 1024 and SV.sam_variant(hip_lib, 2, 64, 64, 5) == (4, False)
+    assert SV.sam_slab_bytes(62, 62, 4) == 62000 > 60 * 1024 >= SV.sam_slab_bytes(61, 62, 4) == 61004
+    assert SV.sam_variant(hip_lib, 2, 62, 62, 5) == (4, False) and SV.sam_variant(hip_lib, 2, 61, 62, 5) == (4, True)
+    assert SV.sam_variant(hip_lib, 1023, 4, 4, 16) == (4, True) and SV.sam_variant(hip_lib, 1024, 4, 4, 16) == (16, True)
+    assert SV.sam_variant(hip_lib, 1, 32, 32, 272) == (4, True)      # the largest shape of test_gpu_ops.test_softargmax2d: 17 groups
+    # the fused read-out (rule R5b) has no unstaged variant: it refuses above 128 KiB of 16 channel lanes, and the planner
+    # (pure Python: it plans without the library) keeps the same limit -- a sweep over map sizes on both sides of it
+    from deephar_amd.engine import planner
+    sides = set()
+    for h in list(range(1, 64)) + [300]:
+        for w in list(range(1, 64)) + [300]:
+            fits = planner.sam_ctx_slab_bytes(h, w) <= planner.SAM_CTX_MAX_SLAB
+            assert planner.sam_ctx_slab_bytes(h, w) == SV.sam_slab_bytes(h, w, 16)
+            assert SV.sam_ctx_rc(hip_lib, h, w) == (0 if fits else -2), (h, w)
+            sides.add(fits)
+    assert sides == {True, False}
+    # 45 x 45 and 40 x 48 fused; 44 x 48, 40 x 52 and 48 x 48 refused
+    assert [SV.sam_ctx_rc(hip_lib, h, w) for h, w in ((45, 45), (40, 48), (44, 48), (40, 52), (48, 48))] == [0, 0, -2, -2, -2]
 
 
 def test_slab_layouts_are_what_they_claim():
