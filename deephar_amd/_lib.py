@@ -68,6 +68,20 @@ class SamRoute(C.Structure):                     # == struct dh_sam_route (dh_so
     _fields_ = [(n, i32) for n in ('rc', 'channels', 'staged', 'ctx_rc')]
 
 
+class CutSeg(C.Structure):                       # == struct dh_cut_seg (dh_unpack_cut_f32)
+    _fields_ = [('dst', vp)] + [(n, i32) for n in ('ld', 'coff', 'c', 'pad')]
+
+
+class ClipInfo(C.Structure):                     # == struct dh_clip_info (dh_clip_inspect)
+    _fields_ = [(n, i32) for n in ('version', 'world', 'T', 'Tl', 'packed_channels', 'num_cut', 'num_outputs',
+                                   'num_head_outputs')] + [('P', i64)] + \
+               [(n, C.c_uint64) for n in ('frames_offset', 'frames_bytes', 'head_offset', 'head_bytes')]
+
+
+# dh_allgather_fn: (ctx, send, recv, floats per rank, stream) -> 0 on success
+ALLGATHER_FN = C.CFUNCTYPE(C.c_int, vp, vp, vp, i64, vp)
+
+
 # dh_conv_route.kernel
 CONV_GENERAL, CONV_DMA, CONV_SPLIT, CONV_SPLIT_EXT, CONV_HALO, CONV_SKINNY, CONV_FIRST_LAYER = range(1, 8)
 
@@ -141,6 +155,23 @@ SIGNATURES = {
     'dh_plan_output_items': (C.c_int64, [vp, C.c_int]),
     'dh_forward': (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), vp]),
     'dh_forward_host': (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]),
+    'dh_plan_input_ptr': (vp, [vp, C.c_int]),
+    'dh_unpack_cut_f32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int, vp]),
+    'dh_unpack_cut_host': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int]),
+    'dh_unpack_cut_vec4': (C.c_int, [C.c_int] * 4 + [vp, vp]),
+    'dh_clip_inspect': (C.c_int, [vp, C.c_size_t, C.POINTER(ClipInfo)]),
+    'dh_clip_inspect_cut': (C.c_int, [vp, C.c_size_t, C.c_int, C.POINTER(i32), C.POINTER(i32)]),
+    'dh_clip_inspect_output': (C.c_int, [vp, C.c_size_t, C.c_int, C.POINTER(i32), C.POINTER(i32)]),
+    'dh_clip_create': (C.c_int, [vp, C.c_size_t, C.c_int, ALLGATHER_FN, vp, C.POINTER(vp)]),
+    'dh_clip_forward': (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), vp]),
+    'dh_clip_forward_host': (C.c_int, [vp, vp, C.c_int, C.POINTER(vp)]),
+    'dh_clip_destroy': (C.c_int, [vp]),
+    'dh_clip_world': (C.c_int, [vp]),
+    'dh_clip_batch': (C.c_int, [vp]),
+    'dh_clip_num_outputs': (C.c_int, [vp]),
+    'dh_clip_output_items': (C.c_int64, [vp, C.c_int]),
+    'dh_clip_frame_items': (C.c_int64, [vp]),
+    'dh_clip_input_is_u8': (C.c_int, [vp]),
     'dh_graph_begin_capture': (C.c_int, [vp]),
     'dh_graph_end_capture': (C.c_int, [vp, C.POINTER(vp)]),
     'dh_graph_launch': (C.c_int, [vp, vp]),

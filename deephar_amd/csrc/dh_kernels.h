@@ -64,6 +64,9 @@ int launch_zeropad(const float* x, float* y, int B, int H, int W, int C, int OH,
 int launch_depth_from_maps(const float* d, int ldd, const float* h, int ldh, float* z, int ldz, int F, int HW,
                            int J, hipStream_t s);
 
+// plan.hip, for clip.hip: where output i of a plan lies in its arena ([n * npix, C] floats at pixel pitch ld); NULL: no such output
+const float* plan_output_view(const dh_plan* pl, int i, int* ld, int* C, int64_t* npix);
+
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel's code object on ONE device: a process that drives
 // several GPUs (Model(device=...), dh_plan executors on other devices) must raise it on each.  One flag word per call
 // site, one bit per device ordinal; a race sets the attribute twice, which is harmless.

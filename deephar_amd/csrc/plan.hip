@@ -343,12 +343,17 @@ int64_t dh_plan_output_items(const dh_plan* pl, int i) {
   return (pl && i >= 0 && i < (int)pl->outs.size()) ? (int64_t)(pl->outs[i].npix * pl->outs[i].C) : -1;
 }
 
+float* dh_plan_input_ptr(const dh_plan* pl, int i) {
+  return (pl && i >= 0 && i < (int)pl->ins.size() && pl->ins[i].u8 == 0) ? reinterpret_cast<float*>(pl->ins[i].dst) : nullptr;
+}
+
 int dh_forward(dh_plan* pl, const float* const* inputs, int m, float* const* outputs, void* stream) {
   if (pl == nullptr || inputs == nullptr || outputs == nullptr || m <= 0 || m > pl->n) return DH_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   for (size_t i = 0; i < pl->ins.size(); ++i) {
     if (inputs[i] == nullptr) return DH_EINVAL;
     const In& in = pl->ins[i];
+    if (reinterpret_cast<const char*>(inputs[i]) == in.dst) continue;     // written in place (dh_plan_input_ptr)
     if (hipMemcpyAsync(in.dst, inputs[i], in.items * (in.u8 ? 1 : 4) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess)
       return DH_ELAUNCH;
   }
@@ -409,3 +414,15 @@ int dh_forward_host(dh_plan* pl, const float* const* inputs_host, int m, float* 
 }
 
 }  // extern "C"
+
+namespace dh {
+
+// clip.hip: where output i of a plan lies in its arena ([n * npix, C] floats at pixel pitch ld)
+const float* plan_output_view(const dh_plan* pl, int i, int* ld, int* C, int64_t* npix) {
+  if (pl == nullptr || i < 0 || i >= (int)pl->outs.size()) return nullptr;
+  const Out& o = pl->outs[i];
+  *ld = o.ld; *C = o.C; *npix = (int64_t)o.npix;
+  return reinterpret_cast<const float*>(pl->arena + o.off);
+}
+
+}  // namespace dh

@@ -20,6 +20,17 @@ the same layout with one more function id (V4_FUNCTIONS) -- every other plan kee
     weights  the weight image (packed conv / depthwise kernels, BN affines, grids), every tensor 256-byte aligned
 Launch order is the plan's step order, a valid single-stream schedule of the graph; tilings are the bound plan's
 (autotuned) ones, so dh_forward reproduces Model.predict bit for bit.
+
+Clip container (little endian), version 1: a frame-sharded clip model (parallel.ShardedClipModel) as ONE file for
+dh_clip_inspect / dh_clip_create / dh_clip_forward -- the two stage plans and the cut table between them:
+    header   'DHCL' u32 version | u32 world (ranks G) | u32 T (frames per clip) | u32 Tl (= T / world, frames per rank)
+             | u32 packed channels Cp | u64 P (pixels per frame of every cut tensor: prod(shape[:-1])) | u32 #cut | u32 #outputs
+             | u64 frames plan offset | u64 frames plan bytes | u64 head plan offset | u64 head plan bytes (0: no head)
+    cut      per cut tensor, in the order of the head plan's inputs: u32 channel offset in the packed axis | u32 channels
+    outputs  per model output, in model order: u32 kind (0: cut tensor passed through, 1: output of the head plan) | u32 index
+             (of the cut tensor / of the head plan's output)
+    plans    the frames plan blob ('DHPL', above) at the next 256-byte boundary behind the tables, the head plan blob at the
+             next 256-byte boundary behind it; the container ends with the head plan (without one: at that boundary, zero filled)
 """
 import ctypes as C
 import struct
@@ -163,3 +174,42 @@ def dump_plan(model, batch, u8_norm=None):
         b = t.detach().cpu().contiguous().numpy().tobytes()
         image[off:off + len(b)] = b
     return head + ins + outs + b''.join(steps) + bytes(image)
+
+
+CLIP_MAGIC, CLIP_VERSION = b'DHCL', 1
+
+
+def pack_clip(world, T, Tl, packed_channels, pixels, cut, outputs, frames_blob, head_blob=b''):
+    """-> bytes: the clip container (module docstring) around two plan blobs.  cut: [(channel offset, channels)];
+    outputs: [(kind, index)] in model order, kind 0 = cut tensor passed through, 1 = head output.  No device needed."""
+    align = lambda v: (v + 255) & ~255
+    tables = b''.join(struct.pack('<II', int(o), int(c)) for o, c in cut) + \
+        b''.join(struct.pack('<II', int(k), int(i)) for k, i in outputs)
+    head_size = 4 + struct.calcsize('<IIIIIQIIQQQQ')
+    f_off = align(head_size + len(tables))
+    h_off = align(f_off + len(frames_blob))
+    head = CLIP_MAGIC + struct.pack('<IIIIIQIIQQQQ', CLIP_VERSION, int(world), int(T), int(Tl), int(packed_channels), int(pixels),
+                                    len(cut), len(outputs), f_off, len(frames_blob), h_off, len(head_blob))
+    body = head + tables
+    body += bytes(f_off - len(body)) + frames_blob
+    body += bytes(h_off - len(body)) + head_blob
+    return body
+
+
+def dump_clip_plan(sharded, clips, uint8=False):
+    """-> bytes.  The frame stage and the head stage of `sharded` (a parallel.ShardedClipModel) bound for `clips` clips per
+    step, with the cut table, as one clip container.  Needs a HIP device (dump_plan, once per stage)."""
+    info = sharded.info
+    fm, hm = sharded.frame_model, sharded.head_model
+    frames = dump_plan(fm, int(clips), u8_norm=fm.channel_power if uint8 else None)
+    head = dump_plan(hm, int(clips)) if hm is not None else b''
+    pixels = {int(np.prod(shape[:-1])) for (shape, _, _) in info['cut']}
+    assert len(pixels) == 1, pixels                          # parallel.split_frames refuses anything else
+    outputs = []
+    for k in range(len(sharded.model.outputs)):
+        if k in info['passthrough']:
+            outputs.append((0, info['passthrough'][k]))
+        else:
+            outputs.append((1, info['head_outputs'].index(k)))
+    return pack_clip(sharded.world, info['T'], info['Tl'], info['packed_channels'], pixels.pop(),
+                     [(off, c) for (_, off, c) in info['cut']], outputs, frames, head)

@@ -382,6 +382,17 @@ class ShardedClipModel:
             json.dump(info, f)
         return info
 
+    def export_clip_plan(self, path, clips, uint8=False):
+        """Write both stages and the cut table as ONE clip container (engine/serialize.py: 'DHCL') for `clips` clips per
+        step: what dh_clip_create / dh_clip_forward (include/deephar_hip.h) run without Python -- frame plan, the host's
+        all-gather (a callback), one unpack launch, head plan.  The same file serves every rank of `self.world`.  uint8=True:
+        the frame plan takes raw uint8 frames.  Returns the number of bytes written."""
+        from .engine.serialize import dump_clip_plan
+        blob = dump_clip_plan(self, int(clips), uint8=uint8)
+        with open(path, 'wb') as f:
+            f.write(blob)
+        return len(blob)
+
     def predict(self, clips):
         """clips: [N, T, H, W, C] (the same array on every rank).  Returns the model's outputs (host arrays)."""
         info = self.info

@@ -498,6 +498,82 @@ int dh_plan_input_is_u8(const dh_plan* plan, int i);      /* 1: input i takes ra
 int64_t dh_plan_output_items(const dh_plan* plan, int i); /* floats per batch item of output i */
 int dh_forward(dh_plan* plan, const float* const* inputs_dev, int m, float* const* outputs_dev, void* stream);
 int dh_forward_host(dh_plan* plan, const float* const* inputs_host, int m, float* const* outputs_host);
+/* The device address dh_forward copies input i to (float inputs; NULL for a uint8 input or no such input).  A caller that
+ * WRITES its data there (dh_clip_forward's unpack launch does) passes that same address as inputs_dev[i]: dh_forward then
+ * skips the copy of that input -- the strided torch copy per cut tensor that Executor.run_device makes for
+ * deephar_amd/parallel.py's head stage has no counterpart here.  A NULL input stays DH_EINVAL. */
+float* dh_plan_input_ptr(const dh_plan* plan, int i);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The clip boundary in one launch.  Replaces, for a host without Python, what the reference does with Keras slicing
+ * Lambdas between the frame stage and the temporal head (action.py:357-366: the per-frame pose / visibility / feature
+ * tensors of a clip re-assembled on the time axis; spnet.py:219-235: the same per pyramid of an SPNet) and what
+ * deephar_amd/parallel.py's ShardedClipModel does with one strided torch copy per cut tensor.
+ *   gathered : the all-gather's result, rank-major [G, m, Tl, P, Cp] floats (G ranks, m clips, Tl frames per rank, P pixels
+ *              -- joints -- per frame, Cp packed channels)
+ *   segment s: dst_s[n, g * Tl + t, p, 0 : c_s] (pixel pitch ld_s >= c_s floats; columns beyond c_s are not touched)
+ *              = gathered[g, n, t, p, coff_s : coff_s + c_s]
+ * One launch covers all segments; `segs_dev` is a table in DEVICE memory (a segment that leaves the packed axis or whose
+ * pitch is below its channels is skipped by the kernel).  A segment moves 16 bytes per lane when Cp, coff, c and ld are
+ * multiples of 4 and both base addresses are 16-byte aligned, one float per lane otherwise (poses: c = 2 / 3,
+ * confidences: c = 1).  Plain vector loads and stores, no atomics.  Cp <= 8192.
+ * dh_unpack_cut_host: the same index arithmetic as a plain host loop over HOST pointers (segment table included).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_cut_seg { float* dst; int32_t ld; int32_t coff; int32_t c; int32_t pad; } dh_cut_seg;
+int dh_unpack_cut_f32(const float* gathered, int G, int m, int Tl, int64_t P, int Cp, const dh_cut_seg* segs_dev, int nseg,
+                      void* stream);
+int dh_unpack_cut_host(const float* gathered, int G, int m, int Tl, int64_t P, int Cp, const dh_cut_seg* segs, int nseg);
+/* 1 when segment (coff, c, ld) with these base addresses takes the 16-byte path, else 0 */
+int dh_unpack_cut_vec4(int Cp, int coff, int c, int ld, const void* gathered, const void* dst);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Frame-sharded clip models for hosts without Python: the frame stage, ONE all-gather, the temporal head -- what
+ * deephar_amd/parallel.py's ShardedClipModel runs (the reference runs a clip on one GPU:
+ * action.py:357-366, spnet.py:219-235).
+ *   blob   : written by ShardedClipModel.export_clip_plan(path, clips) (layout: deephar_amd/engine/serialize.py, 'DHCL'):
+ *            the cut table and the two plan blobs in one container.
+ *   inspect: GPU-free.  Parses and bounds-checks; every malformed or truncated blob is DH_EINVAL; nothing is allocated.
+ *            dh_clip_inspect_cut / _output read entry i of the two tables of a blob that inspects clean.
+ *   create : this rank's two plans on the current device, the persistent [G, clips, Tl, P, Cp] gather buffer and the
+ *            segment table of the unpack launch.  `gather` is the host's collective:
+ *              all-gather `floats_per_rank` floats from every rank into `recv`, rank-major (rank r's floats at
+ *              recv + r * floats_per_rank), ordered on `stream` (enqueue, do not synchronise); 0 = success.  `send` and
+ *              `recv` are device pointers owned by the dh_clip.  The library never calls RCCL itself and does not link
+ *              it: the collective enters only here (ncclAllGather(send, recv, floats_per_rank, ncclFloat, comm, stream)
+ *              is a complete callback, tools/c_host/predict_clip.c).
+ *            NULL is allowed only when world == 1: the packed tensor is then read where the frame plan left it.
+ *   forward: m <= clips; frames_dev is this rank's [m, Tl, H, W, C] (float32, or uint8 when dh_clip_input_is_u8);
+ *            outputs_dev[k] is a device pointer to the dense float32 [m, ...] output k in MODEL order (NULL: not wanted).
+ *            Enqueued on `stream` in this order: frame plan, gather, ONE dh_unpack_cut_f32 launch (head inputs written in
+ *            place, pass-through outputs written straight to outputs_dev), head plan.  Nothing synchronises.  The segment
+ *            table is uploaded at create and again only when the pass-through pointers differ from the previous call
+ *            (that one call waits for `stream` while the table is read: keep the output pointers when capturing a graph).
+ *            Results are bit-identical to Model.predict of the exporting process.
+ *   forward_host: the same with HOST pointers on an internal stream; returns when done.
+ * Serial form only: the two-slot pipelined form of parallel.py (frame stage of step i + 1 under the collective of step i)
+ * and multi-stream plans are out of scope here.  A dh_clip is not re-entrant.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_clip dh_clip;
+typedef struct dh_clip_info {
+  int32_t version, world, T, Tl, packed_channels, num_cut, num_outputs, num_head_outputs;
+  int64_t P;                                          /* pixels per frame of every cut tensor */
+  uint64_t frames_offset, frames_bytes, head_offset, head_bytes;   /* the two plan blobs inside the container; head_bytes 0: no head */
+} dh_clip_info;
+/* all-gather of `floats_per_rank` floats from every rank, rank-major, stream-ordered on `stream`; world 1: recv = send */
+typedef int (*dh_allgather_fn)(void* ctx, const float* send, float* recv, int64_t floats_per_rank, void* stream);
+int dh_clip_inspect(const void* blob, size_t bytes, dh_clip_info* out);
+int dh_clip_inspect_cut(const void* blob, size_t bytes, int i, int32_t* channel_offset, int32_t* channels);
+int dh_clip_inspect_output(const void* blob, size_t bytes, int k, int32_t* is_head, int32_t* index);
+int dh_clip_create(const void* blob, size_t bytes, int rank, dh_allgather_fn gather, void* ctx, dh_clip** out);
+int dh_clip_forward(dh_clip* clip, const void* frames_dev, int m, float* const* outputs_dev, void* stream);
+int dh_clip_forward_host(dh_clip* clip, const void* frames_host, int m, float* const* outputs_host);
+int dh_clip_destroy(dh_clip* clip);
+int dh_clip_world(const dh_clip* clip);
+int dh_clip_batch(const dh_clip* clip);                     /* clips per step the plans were made for */
+int dh_clip_num_outputs(const dh_clip* clip);
+int64_t dh_clip_output_items(const dh_clip* clip, int k);   /* floats per clip of model output k */
+int64_t dh_clip_frame_items(const dh_clip* clip);           /* elements per clip of this rank's frames: Tl * H * W * C */
+int dh_clip_input_is_u8(const dh_clip* clip);
 
 /* ---------------------------------------------------------------------------------------------------
  * Stream-ordered runtime helpers (no torch types): graphs for launch-bound replay, events for timing.
