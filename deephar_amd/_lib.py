@@ -72,6 +72,17 @@ class CutSeg(C.Structure):                       # == struct dh_cut_seg (dh_unpa
     _fields_ = [('dst', vp)] + [(n, i32) for n in ('ld', 'coff', 'c', 'pad')]
 
 
+class OutSeg(C.Structure):                       # == struct dh_out_seg (dh_pack_outputs_f32)
+    _fields_ = [('src', vp), ('dst', vp), ('npix', i64), ('C', i32), ('ld', i32)]
+
+
+class SchedOp(C.Structure):                      # == struct dh_sched_op (dh_sched_build_ops)
+    _fields_ = [(n, i32) for n in ('kind', 'stream', 'arg', 'entry')]
+
+
+SCHED_LAUNCH, SCHED_RECORD, SCHED_WAIT = range(3)    # dh_sched_op.kind
+
+
 class ClipInfo(C.Structure):                     # == struct dh_clip_info (dh_clip_inspect)
     _fields_ = [(n, i32) for n in ('version', 'world', 'T', 'Tl', 'packed_channels', 'num_cut', 'num_outputs',
                                    'num_head_outputs')] + [('P', i64)] + \
@@ -156,6 +167,13 @@ SIGNATURES = {
     'dh_forward': (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), vp]),
     'dh_forward_host': (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]),
     'dh_plan_input_ptr': (vp, [vp, C.c_int]),
+    'dh_plan_num_streams': (C.c_int, [vp]),
+    'dh_plan_side_stream': (vp, [vp, C.c_int]),
+    'dh_pack_outputs_f32': (C.c_int, [C.POINTER(OutSeg), C.c_int, vp]),
+    'dh_pack_outputs_host': (C.c_int, [C.POINTER(OutSeg), C.c_int]),
+    'dh_pack_outputs_vec4': (C.c_int, [C.c_int, C.c_int, vp, vp]),
+    'dh_sched_build_ops': (C.c_int, [C.c_int] + [C.POINTER(i32)] * 5 + [C.c_int] * 4 + [C.POINTER(SchedOp), C.c_int,
+                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dh_unpack_cut_f32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int, vp]),
     'dh_unpack_cut_host': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int]),
     'dh_unpack_cut_vec4': (C.c_int, [C.c_int] * 4 + [vp, vp]),

@@ -3,10 +3,14 @@
 // The blob is written by deephar_amd/engine/serialize.py (format documented there) from a bound, autotuned plan: the
 // launch list of Model.predict with every device pointer expressed relative to the activation arena or the weight
 // image.  This file owns the two allocations, patches the pointers once and replays the launches in order on the
-// caller's stream -- the same C-ABI entry points the Python executor calls, so the results are the same bits.
+// caller's stream -- the same C-ABI entry points the Python executor calls, so the results are the same bits.  A version-5
+// blob carries the engine's multi-stream schedule: plan_sched.h (GPU-free) turns it into the enqueue program of
+// BoundPlan.launch_all, which dh_forward runs with the caller's stream as stream 0 and the plan's own side streams.  Every
+// forward ends with ONE dh_pack_outputs_f32 launch (out_pack.hip) for all wanted outputs.
 #include <cstring>
 #include <vector>
 #include "dh_kernels.h"
+#include "plan_sched.h"
 
 namespace {
 
@@ -17,6 +21,8 @@ enum Fn { F_CONV, F_DW, F_POOL, F_UPADD, F_ELT, F_SAM, F_CTX, F_DMEANS, F_SAM1D,
 struct Step { int fn; std::vector<unsigned char> payload; };
 struct In { uint64_t tag; size_t items; int u8; char* dst; };   // dst: where dh_forward copies the caller's data (patched)
 struct Out { size_t off, npix; int C, ld; };
+// floats output o of `items` batch items takes in dh_forward_host's staging buffer: rounded up to whole 16-byte runs
+inline size_t stage_floats(const Out& o, int items) { return (o.npix * (size_t)o.C * (size_t)items + 3) & ~(size_t)3; }
 
 }  // namespace
 
@@ -29,8 +35,18 @@ struct dh_plan {
   std::vector<In> ins;
   std::vector<Out> outs;
   std::vector<Step> steps;
-  // dh_forward_host staging (allocated on first use)
-  std::vector<float*> in_dev, out_dev;
+  // version 5: the schedule as an enqueue program (empty: every step in order on the caller's stream), the plan's own side
+  // streams (stream k of the program is side[k - 1]) and one sync event per event id of the program
+  std::vector<dh_sched_op> ops;
+  std::vector<hipStream_t> side;
+  std::vector<hipEvent_t> events;
+  std::vector<dh_out_seg> segs;  // this call's pack table
+  // dh_forward_host staging (allocated on first use): one device buffer per input, ONE device buffer and its pinned host
+  // twin for all outputs
+  std::vector<float*> in_dev;
+  std::vector<float*> out_ptr;   // this call's place of every wanted output inside out_stage
+  float* out_stage = nullptr;
+  float* out_host = nullptr;
   hipStream_t stream = nullptr;
 };
 
@@ -188,7 +204,8 @@ int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
   const uint32_t version = r.get<uint32_t>();
   // version 3 = version 2 + the step records of dh_dwconv2d_strided_f32 / dh_conv2d_transpose2x2_f32 (function ids 19, 20)
   // version 4 = version 3 + the step record of dh_conv2d_transpose2x2_split_f32 (function id 21)
-  if (version < 1 || version > 4) return DH_EINVAL;
+  // version 5 = version 4 + a schedule section between the steps and the weight image (multi-stream plans)
+  if (version < 1 || version > 5) return DH_EINVAL;
   dh_plan* pl = new dh_plan();
   pl->n = r.get<int32_t>();
   pl->arena_bytes = r.get<uint64_t>();
@@ -224,6 +241,35 @@ int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
     st.payload.assign(r.p, r.p + nb);
     r.p += nb;
     pl->steps.push_back(std::move(st));
+  }
+  int nstreams = 1, nevents = 0;
+  if (version >= 5) {
+    // schedule section: u32 nstreams | u32 npre | u32 #entries | u32 #waits | per entry u32 step (0xffffffff: no launch),
+    // u32 stream, u32 flags (bit 0: records an event), u32 #waits of the entry | the waits, entry by entry.  Validated and
+    // turned into the enqueue program by plan_sched.h; only the host is touched here.
+    const uint32_t ns = r.get<uint32_t>(), npre = r.get<uint32_t>(), nent = r.get<uint32_t>(), nwaits = r.get<uint32_t>();
+    if (!r.ok || nent > (uint32_t)dh::kSchedMaxEntries || ns > 0x7fffffffu || npre > nent ||
+        (uint64_t)(r.end - r.p) < 16ull * nent || (uint64_t)(r.end - r.p) - 16ull * nent < 4ull * nwaits)
+      return fail(DH_EINVAL);
+    std::vector<int32_t> step(nent), stream(nent), record(nent), wait_off(nent + 1, 0), waits(nwaits);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nent; ++i) {
+      step[i] = (int32_t)r.get<uint32_t>();
+      const uint32_t s = r.get<uint32_t>(), flags = r.get<uint32_t>(), nw = r.get<uint32_t>();
+      if (s >= ns || flags > 1 || (total += nw) > nwaits) return fail(DH_EINVAL);
+      stream[i] = (int32_t)s;
+      record[i] = (int32_t)flags;
+      wait_off[i + 1] = (int32_t)total;
+    }
+    if (total != nwaits) return fail(DH_EINVAL);
+    for (uint32_t k = 0; k < nwaits; ++k) waits[k] = (int32_t)r.get<uint32_t>();
+    const dh::SchedTable tab = {(int)nent, step.data(), stream.data(), record.data(), wait_off.data(), waits.data(), (int)nwaits,
+                                (int)ns, (int)npre, (int)pl->steps.size()};
+    dh::SchedProgram prog;
+    if (!r.ok || dh::sched_build(tab, &prog) != DH_OK) return fail(DH_EINVAL);
+    pl->ops.swap(prog.ops);
+    nstreams = (int)ns;
+    nevents = prog.nevents;
   }
   if (!r.ok || (size_t)(r.end - r.p) != pl->weight_bytes) return fail(DH_EINVAL);
   if (hipMalloc(&pl->arena, pl->arena_bytes ? pl->arena_bytes : 16) != hipSuccess) return fail(DH_ELAUNCH);
@@ -313,6 +359,18 @@ int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
         }
     }
   }
+  // a multi-stream plan's own streams and events: nstreams - 1 non-blocking streams (sched_build bounds nstreams by 4: the
+  // hardware queues of a process), fork + joins + one event per recording entry + relays
+  for (int k = 1; k < nstreams; ++k) {
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return fail(DH_ELAUNCH);
+    pl->side.push_back(st);
+  }
+  for (int e = 0; e < nevents; ++e) {
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(DH_ELAUNCH);
+    pl->events.push_back(ev);
+  }
   *out = pl;
   return DH_OK;
 }
@@ -320,8 +378,12 @@ int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
 int dh_plan_destroy(dh_plan* pl) {
   if (pl == nullptr) return DH_OK;
   if (pl->stream) hipStreamSynchronize(pl->stream);
+  for (hipStream_t st : pl->side) hipStreamSynchronize(st);
+  for (hipEvent_t ev : pl->events) hipEventDestroy(ev);
+  for (hipStream_t st : pl->side) hipStreamDestroy(st);
   for (float* q : pl->in_dev) hipFree(q);
-  for (float* q : pl->out_dev) hipFree(q);
+  if (pl->out_stage) hipFree(pl->out_stage);
+  if (pl->out_host) hipHostFree(pl->out_host);
   if (pl->stream) hipStreamDestroy(pl->stream);
   if (pl->arena) hipFree(pl->arena);
   if (pl->weights) hipFree(pl->weights);
@@ -357,17 +419,56 @@ int dh_forward(dh_plan* pl, const float* const* inputs, int m, float* const* out
     if (hipMemcpyAsync(in.dst, inputs[i], in.items * (in.u8 ? 1 : 4) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess)
       return DH_ELAUNCH;
   }
-  for (const Step& st : pl->steps) {
-    const int rc = run_step(st, stream);
-    if (rc != DH_OK) return rc;
+  if (pl->ops.empty()) {
+    for (const Step& st : pl->steps) {
+      const int rc = run_step(st, stream);
+      if (rc != DH_OK) return rc;
+    }
+  } else {
+    // the enqueue program of plan_sched.h: stream 0 is the caller's.  The input copies above and the staging launches at
+    // the head of the program run before the fork; the pack launch below runs behind the join.
+    auto S = [&](int k) { return k == 0 ? s : pl->side[(size_t)k - 1]; };
+    int rc = DH_OK;
+    bool forked = false;
+    for (const dh_sched_op& op : pl->ops) {
+      if (op.kind == DH_SCHED_LAUNCH) rc = run_step(pl->steps[(size_t)op.arg], S(op.stream));
+      else if (op.kind == DH_SCHED_RECORD) rc = hipEventRecord(pl->events[(size_t)op.arg], S(op.stream)) == hipSuccess ? DH_OK : DH_ELAUNCH;
+      else rc = hipStreamWaitEvent(S(op.stream), pl->events[(size_t)op.arg], 0) == hipSuccess ? DH_OK : DH_ELAUNCH;
+      if (rc != DH_OK) break;
+      forked = forked || op.kind != DH_SCHED_LAUNCH;          // (the first op that is no launch is the fork's record)
+    }
+    if (rc != DH_OK) {
+      // whatever the side streams were given so far is ordered before the caller's next work: join them anyway
+      for (size_t k = 0; forked && k < pl->side.size(); ++k)
+        if (hipEventRecord(pl->events[k + 1], pl->side[k]) == hipSuccess) hipStreamWaitEvent(s, pl->events[k + 1], 0);
+      return rc;
+    }
   }
+  pl->segs.clear();
   for (size_t i = 0; i < pl->outs.size(); ++i) {
     const Out& o = pl->outs[i];
     if (outputs[i] == nullptr) continue;                      // an output the caller does not want
-    const int rc = dh_copy_channels_f32(reinterpret_cast<const float*>(pl->arena + o.off), o.ld, outputs[i], o.C,
-                                        (int64_t)o.npix * m, o.C, stream);
-    if (rc != DH_OK) return rc;
+    pl->segs.push_back(dh_out_seg{reinterpret_cast<const float*>(pl->arena + o.off), outputs[i], (int64_t)o.npix * m, o.C, o.ld});
   }
+  return dh_pack_outputs_f32(pl->segs.data(), (int)pl->segs.size(), stream);
+}
+
+int dh_plan_num_streams(const dh_plan* pl) { return pl ? 1 + (int)pl->side.size() : 0; }
+void* dh_plan_side_stream(const dh_plan* pl, int k) {
+  return (pl && k >= 1 && k <= (int)pl->side.size()) ? pl->side[(size_t)k - 1] : nullptr;
+}
+
+int dh_sched_build_ops(int n, const int32_t* step, const int32_t* stream, const int32_t* record, const int32_t* wait_off,
+                       const int32_t* waits, int nwaits, int nstreams, int npre, int nsteps, dh_sched_op* ops, int max_ops,
+                       int* nops, int* nevents) {
+  if (nops == nullptr || nevents == nullptr || max_ops < 0 || (max_ops > 0 && ops == nullptr)) return DH_EINVAL;
+  const dh::SchedTable tab = {n, step, stream, record, wait_off, waits, nwaits, nstreams, npre, nsteps};
+  dh::SchedProgram prog;
+  const int rc = dh::sched_build(tab, &prog);
+  if (rc != DH_OK) return rc;
+  *nops = (int)prog.ops.size();
+  *nevents = prog.nevents;
+  for (int i = 0; i < max_ops && i < *nops; ++i) ops[i] = prog.ops[(size_t)i];
   return DH_OK;
 }
 
@@ -377,40 +478,53 @@ int dh_forward_host(dh_plan* pl, const float* const* inputs_host, int m, float* 
     // staging is built in locals and committed only when every allocation succeeded: a failure part-way leaves the plan
     // as it was (the next call tries again) instead of with short in_dev / out_dev vectors
     hipStream_t st = nullptr;
-    std::vector<float*> in_dev, out_dev;
+    std::vector<float*> in_dev;
+    float* out_stage = nullptr;
+    float* out_host = nullptr;
     bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
     for (size_t i = 0; ok && i < pl->ins.size(); ++i) {
       float* q = nullptr;
       ok = hipMalloc(&q, pl->ins[i].items * (pl->ins[i].u8 ? 1 : 4) * (size_t)pl->n) == hipSuccess;
       if (ok) in_dev.push_back(q);
     }
-    for (size_t i = 0; ok && i < pl->outs.size(); ++i) {
-      float* q = nullptr;
-      ok = hipMalloc(&q, pl->outs[i].npix * pl->outs[i].C * 4 * (size_t)pl->n) == hipSuccess;
-      if (ok) out_dev.push_back(q);
-    }
+    size_t stage = 0;                                         // floats: every output of a full batch, each from a 16-byte boundary
+    for (const Out& o : pl->outs) stage += stage_floats(o, pl->n);
+    ok = ok && hipMalloc(&out_stage, stage * 4) == hipSuccess;
+    ok = ok && hipHostMalloc(&out_host, stage * 4, hipHostMallocDefault) == hipSuccess;
     if (!ok) {
       for (float* q : in_dev) hipFree(q);
-      for (float* q : out_dev) hipFree(q);
+      if (out_stage) hipFree(out_stage);
+      if (out_host) hipHostFree(out_host);
       if (st) hipStreamDestroy(st);
       return DH_ELAUNCH;
     }
     pl->in_dev.swap(in_dev);
-    pl->out_dev.swap(out_dev);
+    pl->out_stage = out_stage;
+    pl->out_host = out_host;
     pl->stream = st;
   }
   for (size_t i = 0; i < pl->ins.size(); ++i)
     if (hipMemcpyAsync(pl->in_dev[i], inputs_host[i], pl->ins[i].items * (pl->ins[i].u8 ? 1 : 4) * (size_t)m,
                        hipMemcpyHostToDevice, pl->stream) != hipSuccess)
       return DH_ELAUNCH;
-  const int rc = dh_forward(pl, pl->in_dev.data(), m, pl->out_dev.data(), pl->stream);
-  if (rc != DH_OK) return rc;
+  // the wanted outputs of THIS call back to back in the staging buffer (the pack launch of dh_forward writes them there),
+  // ONE device-to-host copy of exactly those floats, then a host-side scatter
+  pl->out_ptr.assign(pl->outs.size(), nullptr);
+  size_t used = 0;
   for (size_t i = 0; i < pl->outs.size(); ++i)
-    if (outputs_host[i] != nullptr &&
-        hipMemcpyAsync(outputs_host[i], pl->out_dev[i], pl->outs[i].npix * pl->outs[i].C * 4 * (size_t)m,
-                       hipMemcpyDeviceToHost, pl->stream) != hipSuccess)
-      return DH_ELAUNCH;
-  return hipStreamSynchronize(pl->stream) == hipSuccess ? DH_OK : DH_ELAUNCH;
+    if (outputs_host[i] != nullptr) {
+      pl->out_ptr[i] = pl->out_stage + used;
+      used += stage_floats(pl->outs[i], m);
+    }
+  const int rc = dh_forward(pl, pl->in_dev.data(), m, pl->out_ptr.data(), pl->stream);
+  if (rc != DH_OK) return rc;
+  if (used != 0 && hipMemcpyAsync(pl->out_host, pl->out_stage, used * 4, hipMemcpyDeviceToHost, pl->stream) != hipSuccess)
+    return DH_ELAUNCH;
+  if (hipStreamSynchronize(pl->stream) != hipSuccess) return DH_ELAUNCH;
+  for (size_t i = 0; i < pl->outs.size(); ++i)
+    if (outputs_host[i] != nullptr)
+      std::memcpy(outputs_host[i], pl->out_host + (pl->out_ptr[i] - pl->out_stage), pl->outs[i].npix * pl->outs[i].C * 4 * (size_t)m);
+  return DH_OK;
 }
 
 }  // extern "C"

@@ -21,6 +21,20 @@ the same layout with one more function id (V4_FUNCTIONS) -- every other plan kee
 Launch order is the plan's step order, a valid single-stream schedule of the graph; tilings are the bound plan's
 (autotuned) ones, so dh_forward reproduces Model.predict bit for bit.
 
+Version 5 (dump_plan(..., multi_stream=True) of a plan with more than one stream -- Model.num_streams > 1; every other export,
+a several-stream plan under the default keyword included, stays the version 2 - 4 blob it was, byte for byte): the same layout
+with a schedule section between the steps and the weight image, the engine's multi-stream schedule for dh_forward:
+    schedule u32 nstreams | u32 npre (leading entries that stage the inputs: launched on stream 0 in front of the fork)
+             | u32 #entries | u32 #waits (of all entries)
+             per entry (one per bound call of the exporter, absorbed no-ops included, in launch order):
+               u32 step (index into `steps`, or 0xffffffff: no launch -- the call's work moved into an earlier grouped /
+               paired launch; it keeps its entry so that it still records its event at its own place)
+               | u32 stream | u32 flags (bit 0: an event is recorded behind it) | u32 #waits of this entry
+             waits   u32 entry index per wait, entry by entry: an EARLIER entry on another stream that records
+The library turns the table into the enqueue program of BoundPlan.launch_all (csrc/plan_sched.h: fork, per-entry waits /
+launch / record, the relay rule, join) and refuses a table that breaks one of the rules above, more than 4 streams, or sizes
+that do not add up.
+
 Clip container (little endian), version 1: a frame-sharded clip model (parallel.ShardedClipModel) as ONE file for
 dh_clip_inspect / dh_clip_create / dh_clip_forward -- the two stage plans and the cut table between them:
     header   'DHCL' u32 version | u32 world (ranks G) | u32 T (frames per clip) | u32 Tl (= T / world, frames per rank)
@@ -115,10 +129,52 @@ def blob_version(function_ids):
     return 4 if top >= len(FUNCTIONS) else (3 if top >= V3_FUNCTIONS else VERSION)
 
 
-def dump_plan(model, batch, u8_norm=None):
+SCHEDULE_VERSION = 5            # blob version of a plan written with its multi-stream schedule
+NO_LAUNCH = 0xffffffff          # schedule entry whose work moved into an earlier grouped / paired launch
+
+
+def schedule_entries(steps, npre=0, noop=()):
+    """-> [(blob step index or None, stream, records, [entry indices it waits for])], one per bound call.  steps: the Step of
+    every call in launch order (BoundPlan.calls; a Plan's steps for a plan that is not bound: npre = 0); npre: the leading
+    input-staging calls; noop: indices of calls absorbed into an earlier launch (BoundPlan.noop_calls).  Step.wait holds
+    plan-step indices: call index = plan-step index + npre, as in BoundPlan.launch_all.  No device needed."""
+    entries, launched = [], 0
+    for i, st in enumerate(steps):
+        idx = None
+        if i not in noop:
+            idx, launched = launched, launched + 1
+        entries.append((idx, int(st.stream), bool(st.record), [int(w) + npre for w in st.wait]))
+    return entries
+
+
+def pack_schedule(entries, nstreams, npre=0):
+    """-> bytes: the schedule section of a version-5 blob (module docstring).  No device needed."""
+    waits = [w for e in entries for w in e[3]]
+    head = struct.pack('<IIII', int(nstreams), int(npre), len(entries), len(waits))
+    body = b''.join(struct.pack('<IIII', NO_LAUNCH if idx is None else idx, stream, 1 if record else 0, len(ws))
+                    for idx, stream, record, ws in entries)
+    return head + body + struct.pack('<%dI' % len(waits), *waits)
+
+
+def schedule_section(steps, nstreams, npre=0, noop=(), multi_stream=False):
+    """-> the schedule section dump_plan writes: b'' (the blob keeps its version) unless the caller asked for the multi-stream
+    schedule AND the plan has more than one stream.  No device needed."""
+    if not multi_stream or nstreams <= 1:
+        return b''
+    return pack_schedule(schedule_entries(steps, npre, noop), nstreams, npre)
+
+
+def plan_version(function_ids, section=b''):
+    """The version dump_plan writes: SCHEDULE_VERSION with a schedule section, blob_version otherwise."""
+    return SCHEDULE_VERSION if section else blob_version(function_ids)
+
+
+def dump_plan(model, batch, u8_norm=None, multi_stream=False):
     """-> bytes.  `model`'s plan bound (and autotuned) for `batch`; needs a HIP device (the weight image is read back).
     u8_norm: None for float inputs; a channel_power (as for Executor.bind) for a plan that takes raw uint8 frames and
-    normalises them on the GPU (inside the first convolution where the planner could fuse it)."""
+    normalises them on the GPU (inside the first convolution where the planner could fuse it).
+    multi_stream: write the plan's stream schedule too (version 5) when it has more than one stream; False (the default) and
+    one-stream plans give the blob of versions 2 - 4, byte for byte."""
     ex = model.executor
     torch = __import__('torch')
     with torch.cuda.device(ex.device), torch.cuda.stream(ex.stream):
@@ -155,7 +211,8 @@ def dump_plan(model, batch, u8_norm=None):
             payload = _scalars(sig, args, reg)
         steps.append(struct.pack('<II', names[name], len(payload)) + payload)
     plan = bp.plan
-    version = blob_version(struct.unpack_from('<I', st)[0] for st in steps)
+    section = schedule_section([c[2] for c in bp.calls], plan.nstreams, bp.npre, bp.noop_calls, multi_stream)
+    version = plan_version((struct.unpack_from('<I', st)[0] for st in steps), section)
     head = MAGIC + struct.pack('<IiQQIIIQ', version, bp.n, bp.arena.numel() * 4, (reg.size + 255) & ~255,
                                len(plan.inputs), len(plan.outputs), len(steps), reg.u8_size)
     ins = b''
@@ -173,7 +230,7 @@ def dump_plan(model, batch, u8_norm=None):
     for off, t in reg.image:
         b = t.detach().cpu().contiguous().numpy().tobytes()
         image[off:off + len(b)] = b
-    return head + ins + outs + b''.join(steps) + bytes(image)
+    return head + ins + outs + b''.join(steps) + section + bytes(image)
 
 
 CLIP_MAGIC, CLIP_VERSION = b'DHCL', 1
@@ -196,13 +253,14 @@ def pack_clip(world, T, Tl, packed_channels, pixels, cut, outputs, frames_blob, 
     return body
 
 
-def dump_clip_plan(sharded, clips, uint8=False):
+def dump_clip_plan(sharded, clips, uint8=False, multi_stream=False):
     """-> bytes.  The frame stage and the head stage of `sharded` (a parallel.ShardedClipModel) bound for `clips` clips per
-    step, with the cut table, as one clip container.  Needs a HIP device (dump_plan, once per stage)."""
+    step, with the cut table, as one clip container.  Needs a HIP device (dump_plan, once per stage).  multi_stream goes to
+    both stage plans (dump_plan): a stage whose model has num_streams > 1 is written with its schedule."""
     info = sharded.info
     fm, hm = sharded.frame_model, sharded.head_model
-    frames = dump_plan(fm, int(clips), u8_norm=fm.channel_power if uint8 else None)
-    head = dump_plan(hm, int(clips)) if hm is not None else b''
+    frames = dump_plan(fm, int(clips), u8_norm=fm.channel_power if uint8 else None, multi_stream=multi_stream)
+    head = dump_plan(hm, int(clips), multi_stream=multi_stream) if hm is not None else b''
     pixels = {int(np.prod(shape[:-1])) for (shape, _, _) in info['cut']}
     assert len(pixels) == 1, pixels                          # parallel.split_frames refuses anything else
     outputs = []

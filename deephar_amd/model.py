@@ -208,13 +208,16 @@ class Model:
         from . import weights as W
         W.save_weights(self, filepath)
 
-    def export_plan(self, filepath, batch_size, uint8=False):
+    def export_plan(self, filepath, batch_size, uint8=False, multi_stream=False):
         """Write the bound, autotuned launch list + weight image of this model for `batch_size` items: the blob the
         C-level executor of the library runs without Python (dh_plan_create / dh_forward, include/deephar_hip.h;
         INTEGRATION.md shows a C host).  uint8=True: the plan takes raw uint8 frames (what `predict` does with uint8
-        arrays: normalised on the GPU with `self.channel_power`).  Returns the number of bytes written."""
+        arrays: normalised on the GPU with `self.channel_power`).  multi_stream=True: a model with num_streams > 1 is
+        written with its stream schedule (blob version 5) and dh_forward runs it on that many streams, the caller's
+        included -- the latency regime's 'tail' policy for a C host; by default, and for a one-stream model, the blob is the
+        one-stream order of versions 2 - 4.  Returns the number of bytes written."""
         from .engine.serialize import dump_plan
-        blob = dump_plan(self, int(batch_size), u8_norm=self.channel_power if uint8 else None)
+        blob = dump_plan(self, int(batch_size), u8_norm=self.channel_power if uint8 else None, multi_stream=multi_stream)
         with open(filepath, 'wb') as f:
             f.write(blob)
         return len(blob)

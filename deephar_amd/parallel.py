@@ -382,13 +382,14 @@ class ShardedClipModel:
             json.dump(info, f)
         return info
 
-    def export_clip_plan(self, path, clips, uint8=False):
+    def export_clip_plan(self, path, clips, uint8=False, multi_stream=False):
         """Write both stages and the cut table as ONE clip container (engine/serialize.py: 'DHCL') for `clips` clips per
         step: what dh_clip_create / dh_clip_forward (include/deephar_hip.h) run without Python -- frame plan, the host's
         all-gather (a callback), one unpack launch, head plan.  The same file serves every rank of `self.world`.  uint8=True:
-        the frame plan takes raw uint8 frames.  Returns the number of bytes written."""
+        the frame plan takes raw uint8 frames.  multi_stream=True: a stage whose model has num_streams > 1 is written with its
+        stream schedule (Model.export_plan).  Returns the number of bytes written."""
         from .engine.serialize import dump_clip_plan
-        blob = dump_clip_plan(self, int(clips), uint8=uint8)
+        blob = dump_clip_plan(self, int(clips), uint8=uint8, multi_stream=multi_stream)
         with open(path, 'wb') as f:
             f.write(blob)
         return len(blob)

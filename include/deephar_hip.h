@@ -486,6 +486,19 @@ int dh_depth_from_maps_f32(const float* d, int ldd, const float* h, int ldh, flo
  * utils/transform.normalize_channels, inside the first convolution where possible): dh_plan_input_is_u8(plan, i) == 1 and
  * inputs[i] points to m * dh_plan_input_items(plan, i) BYTES (cast the uint8 pointer to const float*).
  * rc != 0 -> the host raises its own error.
+ * Multi-stream plans (Model.export_plan(path, batch, multi_stream=True) of a model with num_streams > 1: blob version 5,
+ * the same layout plus a schedule section): create validates the section (a malformed or truncated one is DH_EINVAL),
+ * opens dh_plan_num_streams(plan) - 1 non-blocking streams of the plan's own and the events that order them.  forward
+ * runs the engine's enqueue program with the caller's stream as stream 0: input copies and input staging, fork, every
+ * step on its scheduled stream with event waits for the cross-stream dependencies, join -- everything the side streams
+ * did is ordered before whatever the caller enqueues on `stream` next, so the contract above does not change and the
+ * results are the same bits.  If a launch fails behind the fork the side streams are still joined before the code is
+ * returned.  A plan has at most 4 streams, the caller's included: every stream a process opens takes one of ROCm's four
+ * hardware queues (GPU_MAX_HW_QUEUES), and the library never raises that number -- a host that keeps streams of its own
+ * counts them against the same four.  Without multi_stream=True every blob is the one-stream order it always was.
+ * ROCm 7.2 quirk 2: the graph exec of a capture that spans several streams cannot be destroyed
+ * safely, and dh_graph_destroy would do just that -- capturing a multi-stream dh_forward is neither promised nor tested;
+ * run it eagerly (the two-stream forward costs the same device time eager and replayed).
  * ------------------------------------------------------------------------------------------------- */
 typedef struct dh_plan dh_plan;
 int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** plan_out);
@@ -503,6 +516,51 @@ int dh_forward_host(dh_plan* plan, const float* const* inputs_host, int m, float
  * skips the copy of that input -- the strided torch copy per cut tensor that Executor.run_device makes for
  * deephar_amd/parallel.py's head stage has no counterpart here.  A NULL input stays DH_EINVAL. */
 float* dh_plan_input_ptr(const dh_plan* plan, int i);
+int dh_plan_num_streams(const dh_plan* plan);             /* streams a forward runs on, the caller's included (1: versions 1 - 4) */
+/* test aid, like dh_stream_spin_us: the plan's own side stream k (1 <= k < dh_plan_num_streams), so a test can delay it
+ * against the caller's stream; NULL for any other k.  The handle belongs to the plan. */
+void* dh_plan_side_stream(const dh_plan* plan, int k);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Every wanted output of a forward in one launch: the counterpart of dh_unpack_cut_f32 at the other end.  dh_forward ends
+ * with it (instead of one dh_copy_channels_f32 launch per output), dh_forward_host packs all outputs into one staging
+ * buffer with it and reads them back with ONE device-to-host copy.
+ *   segment s: dst_s[p * C_s + c] = src_s[p * ld_s + c] for p < npix_s, c < C_s  (npix = pixels per batch item x items;
+ *              ld >= C floats; the columns beyond C of the source are not read)
+ * `segs` is a table in HOST memory: the segments travel by value in the kernel arguments, at most 64 per launch (more go
+ * out as further launches), so nothing is uploaded per call and the launch is capturable.  A segment whose dst is NULL is
+ * dropped before the launch.  A segment moves 16 bytes per lane when C and ld are multiples of 4 and both base addresses
+ * are 16-byte aligned, one float per lane otherwise (poses: C = 2 / 3, confidences: C = 1, action scores: npix = items);
+ * work-groups are dealt to the segments by a prefix table over those units.  Plain vector loads and stores, no atomics.
+ * dh_pack_outputs_host: the same index arithmetic as a plain host loop over HOST pointers.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_out_seg { const float* src; float* dst; int64_t npix; int32_t C; int32_t ld; } dh_out_seg;
+int dh_pack_outputs_f32(const dh_out_seg* segs, int nseg, void* stream);
+int dh_pack_outputs_host(const dh_out_seg* segs, int nseg);
+/* 1 when a segment (C, ld) with these base addresses takes the 16-byte path, else 0 */
+int dh_pack_outputs_vec4(int C, int ld, const void* src, const void* dst);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The schedule of a multi-stream plan as an enqueue program, GPU-free (csrc/plan_sched.h; dh_plan_create and dh_forward
+ * run exactly this).  Table: n schedule entries -- step[i] the blob step entry i launches or -1 (its work moved into an
+ * earlier grouped / paired launch), stream[i], record[i] != 0 when an event is recorded behind it, and the earlier entries
+ * waits[wait_off[i] .. wait_off[i + 1]) it waits for; the first npre entries are input staging; the launching entries name
+ * the steps 0 .. nsteps - 1 in order.  DH_EINVAL unless 1 <= nstreams <= 4, every stream < nstreams, the staging entries
+ * are on stream 0 without waits or events, every wait names an EARLIER entry that records and sits on ANOTHER stream, and
+ * the table sizes agree (wait_off[0] == 0, ascending, wait_off[n] == nwaits).
+ * Program: LAUNCH of the staging entries | RECORD fork on stream 0, WAIT fork on every side stream | per entry its WAITs,
+ * its LAUNCH (none for -1), its RECORD | per side stream RECORD join on it, WAIT join on stream 0.  A side stream never
+ * waits directly on an event of a higher-numbered side stream: stream 0 waits and re-records it on a relay event.
+ * Event ids: 0 fork, k the join of side stream k, then one per recording entry, then the relays; *nevents counts them.
+ * *nops receives the length of the program; at most max_ops ops are written to `ops` (which may be NULL).
+ * ------------------------------------------------------------------------------------------------- */
+#define DH_SCHED_LAUNCH 0 /* arg: blob step */
+#define DH_SCHED_RECORD 1 /* arg: event id */
+#define DH_SCHED_WAIT 2   /* arg: event id */
+typedef struct dh_sched_op { int32_t kind; int32_t stream; int32_t arg; int32_t entry; /* -1: fork / join */ } dh_sched_op;
+int dh_sched_build_ops(int n, const int32_t* step, const int32_t* stream, const int32_t* record, const int32_t* wait_off,
+                       const int32_t* waits, int nwaits, int nstreams, int npre, int nsteps, dh_sched_op* ops, int max_ops,
+                       int* nops, int* nevents);
 
 /* ---------------------------------------------------------------------------------------------------
  * The clip boundary in one launch.  Replaces, for a host without Python, what the reference does with Keras slicing
@@ -551,7 +609,8 @@ int dh_unpack_cut_vec4(int Cp, int coff, int c, int ld, const void* gathered, co
  *            Results are bit-identical to Model.predict of the exporting process.
  *   forward_host: the same with HOST pointers on an internal stream; returns when done.
  * Serial form only: the two-slot pipelined form of parallel.py (frame stage of step i + 1 under the collective of step i)
- * and multi-stream plans are out of scope here.  A dh_clip is not re-entrant.
+ * is out of scope here.  Either stage may be a multi-stream plan (export_clip_plan(path, clips, multi_stream=True)): its
+ * dh_forward forks from and joins back into `stream`, so the order above holds.  A dh_clip is not re-entrant.
  * ------------------------------------------------------------------------------------------------- */
 typedef struct dh_clip dh_clip;
 typedef struct dh_clip_info {
