@@ -76,7 +76,15 @@ class OutSeg(C.Structure):                       # == struct dh_out_seg (dh_pack
     _fields_ = [('src', vp), ('dst', vp), ('npix', i64), ('C', i32), ('ld', i32)]
 
 
-class SchedOp(C.Structure):                      # == struct dh_sched_op (dh_sched_build_ops)
+class CropSrc(C.Structure):                      # == struct dh_crop_src (dh_crop_program_build_host)
+    _fields_ = [('ptr', vp), ('pitch', i64), ('H', i32), ('W', i32)]
+
+
+class CropJob(C.Structure):                      # == struct dh_crop_job
+    _fields_ = [(n, i32) for n in ('src', 'x0', 'y0', 'x1', 'y1', 'hflip')]
+
+
+class SchedOp(C.Structure):                     # == struct dh_sched_op (dh_sched_build_ops)
     _fields_ = [(n, i32) for n in ('kind', 'stream', 'arg', 'entry')]
 
 
@@ -172,7 +180,14 @@ SIGNATURES = {
     'dh_pack_outputs_f32': (C.c_int, [C.POINTER(OutSeg), C.c_int, vp]),
     'dh_pack_outputs_host': (C.c_int, [C.POINTER(OutSeg), C.c_int]),
     'dh_pack_outputs_vec4': (C.c_int, [C.c_int, C.c_int, vp, vp]),
-    'dh_sched_build_ops': (C.c_int, [C.c_int] + [C.POINTER(i32)] * 5 + [C.c_int] * 4 + [C.POINTER(SchedOp), C.c_int,
+    'dh_crop_program_bytes': (C.c_int, [C.POINTER(CropJob), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'dh_crop_program_build_host': (C.c_int, [C.POINTER(CropSrc), C.c_int, C.POINTER(CropJob), C.c_int, C.c_int, C.c_int, vp,
+                                             C.c_size_t]),
+    'dh_crop_resize_u8': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp]),
+    'dh_crop_resize_host': (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, i64]),
+    'dh_crop_axis_taps': (C.c_int, [C.c_int, C.c_int]),
+    'dh_crop_axis_coeffs_host': (C.c_int, [C.c_int] * 3 + [C.POINTER(i32)] * 3),
+    'dh_sched_build_ops':(C.c_int, [C.c_int] + [C.POINTER(i32)] * 5 + [C.c_int] * 4 + [C.POINTER(SchedOp), C.c_int,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dh_unpack_cut_f32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int, vp]),
     'dh_unpack_cut_host': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int]),

@@ -789,23 +789,37 @@ class Executor:
         return self.run_pipelined(arrays, n or arrays[0].shape[0], u8_norm=u8_norm)
 
     # ---- the Model.predict boundary: host arrays in, host arrays out ---------------------------------------------
-    def _io(self, bp, depth):
+    def _io(self, bp, depth, staged=True):
         """Per bound plan: a ring of `depth` slots of pinned host staging (inputs in the dtype that crosses PCIe: uint8
         frames or float32 -- float64 loader arrays are cast on the HOST while being copied into the pinned buffer),
-        their device twins, one pinned buffer per slot for the packed outputs, and the events ordering the streams."""
+        their device twins, one pinned buffer per slot for the packed outputs, and the events ordering the streams.
+        staged=False (the crop front end writes the plan's input itself): no input staging is allocated; the slots hold
+        the crop programs instead (_crop_slots)."""
         io = getattr(bp, '_io', None)
         if io is None:
-            io = bp._io = dict(host_in=[], dev_in=[], host_out=[], h2d=[], done=[], pending=[])
+            io = bp._io = dict(host_in=[], dev_in=[], host_out=[], h2d=[], done=[], pending=[], prog_host=[], prog_dev=[])
         torch = _torch()
         dt = torch.uint8 if bp.u8 is not None else torch.float32
-        while len(io['host_in']) < depth:
+        while staged and len(io['host_in']) < depth:
             io['host_in'].append([torch.empty((bp.n,) + v.shape, dtype=dt, pin_memory=True) for v in self.plan.inputs])
             io['dev_in'].append([torch.empty((bp.n,) + v.shape, dtype=dt, device=self.device) for v in self.plan.inputs])
+        while len(io['host_out']) < depth:
             io['host_out'].append(torch.empty(max(self.plan.out_items * bp.n, 4), dtype=torch.float32, pin_memory=True))
             io['h2d'].append(torch.cuda.Event())
             io['done'].append(torch.cuda.Event())
             io['pending'].append(None)
         return io
+
+    def _crop_slots(self, io, depth, nbytes):
+        """Per slot: pinned host memory for a chunk's crop program and its device twin, at least `nbytes` each."""
+        torch = _torch()
+        for k in range(depth):
+            if k >= len(io['prog_host']):
+                io['prog_host'].append(None)
+                io['prog_dev'].append(None)
+            if io['prog_host'][k] is None or io['prog_host'][k].numel() < nbytes:
+                io['prog_host'][k] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                io['prog_dev'][k] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
 
     def _host_outputs(self, bp, flat, m):
         """Slice the packed output region (host copy of arena[0 : out_items * n]) into one fresh array per output."""
@@ -822,11 +836,11 @@ class Executor:
             outs.append(np.array(view[:m].numpy(), dtype=np.float32, copy=True, order='C'))
         return outs
 
-    def run_pipelined(self, arrays, bs, u8_norm=None, verbose=0):
+    def run_pipelined(self, arrays, bs, u8_norm=None, verbose=0, crop=None):
         with self._lock:          # one thread at a time on the shared stream (engine/executor.py: stream_lock)
-            return self._run_pipelined_locked(arrays, bs, u8_norm, verbose)
+            return self._run_pipelined_locked(arrays, bs, u8_norm, verbose, crop)
 
-    def _run_pipelined_locked(self, arrays, bs, u8_norm=None, verbose=0):
+    def _run_pipelined_locked(self, arrays, bs, u8_norm=None, verbose=0, crop=None):
         """Forward over all rows of `arrays` (host arrays, equal leading dim) in chunks of `bs`, as a 3-stage pipeline:
              host   : cast / copy chunk i+2 into pinned staging on a small THREAD POOL (row slices in parallel; the
                       copy releases the GIL) while the main thread enqueues chunk i -- a float32 batch of 64 frames is
@@ -839,10 +853,22 @@ class Executor:
            pinned staging per bound plan): on this stack every host-side wait that actually has to block is followed by
            a 40-70 ms hole in the GPU's timeline, even though later chunks are already queued
            (profiles/r02_predict_boundary.md) -- so the host enqueues ahead and waits as late as it can.
+           crop (frontend.CropFeed; `arrays` is None): the input is cropped out of device-resident full frames instead of
+           copied in.  host: chunk i+2's crop program (source table, jobs, coefficient tables) is built into pinned memory
+           on the pool; copy: the program goes to the device; compute: ONE dh_crop_resize_u8 launch writes the chunk's
+           crops straight into the plan's uint8 input, then the same forward and D2H.  Same slots, same events, no host
+           synchronisation between chunks.
            Returns one np.float32 array per model output, rows in input order (keras Model.predict semantics:
            exp/common/*_tools.py; timing method of exp/pennaction/eval_speed2d.py:70-77)."""
         torch = _torch()
-        total = arrays[0].shape[0]
+        if crop is not None:
+            if len(self.plan.inputs) != 1 or u8_norm is None:
+                raise ValueError('the crop front end feeds a single uint8 image input')
+            v0 = self.plan.inputs[0]
+            if tuple(v0.shape[-3:]) != (crop.OH, crop.OW, 3) or int(np.prod(v0.shape[:-3], dtype=np.int64)) != crop.per_item:
+                raise ValueError('crops of %d x [%d, %d, 3] do not fill the model input %s' %
+                                 (crop.per_item, crop.OH, crop.OW, tuple(v0.shape)))
+        total = arrays[0].shape[0] if crop is None else crop.total
         bs = int(min(bs, total))
         nchunks = (total + bs - 1) // bs
         with torch.cuda.device(self.device):
@@ -858,7 +884,9 @@ class Executor:
             slot_bytes = sum(bs * int(np.prod(v.shape)) for v in self.plan.inputs) * (1 if want == torch.uint8 else 4)
             depth = max(2, min(nchunks, int(os.environ.get('DEEPHAR_PREDICT_DEPTH', '8')),
                                max(2, (512 << 20) // max(slot_bytes, 1))))
-            io = self._io(bp, depth)
+            io = self._io(bp, depth, staged=crop is None)
+            if crop is not None:        # (the size query refuses a window beyond the scale cap before anything is enqueued)
+                self._crop_slots(io, depth, max(crop.program_bytes(c0, min(bs, total - c0)) for c0 in range(0, total, bs)))
             io['pending'] = [None] * len(io['pending'])        # a call that died mid-loop must not leak rows into this one
             results = []
             ahead = min(2, depth - 1)                           # chunks staged ahead of the one being enqueued
@@ -877,6 +905,8 @@ class Executor:
                 slot, start = ci % depth, ci * bs
                 collect(slot)                                   # chunk ci - depth used this slot (its H2D is long done)
                 m = min(bs, total - start)
+                if crop is not None:                            # the chunk's crop program, built off the main thread
+                    return m, None, None, [pool.submit(crop.build, start, m, io['prog_host'][slot])]
                 on_dev, dev_src, futs = [], [], []
                 for k, (v, arr) in enumerate(zip(self.plan.inputs, arrays)):
                     part = arr[start:start + m]
@@ -904,12 +934,14 @@ class Executor:
                         staged[ci + ahead] = stage(ci + ahead)
                     slot = ci % depth
                     m, on_dev, dev_src, futs = staged.pop(ci)
-                    for fu in futs:
-                        fu.result()
+                    staged_now = [fu.result() for fu in futs]
+                    nprog = staged_now[0] if crop is not None else 0         # bytes of the chunk's crop program
                     with torch.cuda.stream(self.copy_stream):
-                        if any(on_dev):                         # the caller's device data may still be in flight on ITS stream
+                        if crop is not None:
+                            io['prog_dev'][slot][:nprog].copy_(io['prog_host'][slot][:nprog], non_blocking=True)
+                        elif any(on_dev):                         # the caller's device data may still be in flight on ITS stream
                             self.copy_stream.wait_stream(torch.cuda.current_stream())
-                        for k in range(len(arrays)):
+                        for k in range(len(arrays) if crop is None else 0):
                             src = dev_src[k] if on_dev[k] else io['host_in'][slot][k][:m]
                             io['dev_in'][slot][k][:m].copy_(src, non_blocking=True)
                         io['h2d'][slot].record(self.copy_stream)
@@ -917,6 +949,11 @@ class Executor:
                         self.stream.wait_event(io['h2d'][slot])                       # GPU-side wait
                         for k, v in enumerate(self.plan.inputs):
                             dst = bp.u8[id(v.buf)][0] if bp.u8 is not None else bp.tensor(v)
+                            if crop is not None:                # no intermediate tensor: the launch fills the plan's input
+                                _lib.check(bp.lib.dh_crop_resize_u8(io['prog_dev'][slot].data_ptr(), m * crop.per_item, crop.OH,
+                                                                    crop.OW, dst.data_ptr(), crop.OH * crop.OW * 3,
+                                                                    self.stream_ptr), 'dh_crop_resize_u8')
+                                continue
                             dst[:m].copy_(io['dev_in'][slot][k][:m], non_blocking=True)
                         self.forward(bp)
                         io['host_out'][slot].copy_(bp.arena[:io['host_out'][slot].numel()], non_blocking=True)

@@ -10,7 +10,7 @@ from types import SimpleNamespace
 
 from . import action, bbox, pose
 
-mpii_tools = SimpleNamespace(refine_pred=bbox.refine_pred, absulute_pred=pose.absulute_pred,
+mpii_tools = SimpleNamespace(refine_pred=bbox.refine_pred, refine_pred_frames=bbox.refine_pred_frames, absulute_pred=pose.absulute_pred,
                              eval_singleperson_pckh=pose.eval_singleperson_pckh)
 h36m_tools = SimpleNamespace(eval_human36m_sc_error=pose.eval_human36m_sc_error)
 penn_tools = SimpleNamespace(eval_singleclip_gt_bbox=action.eval_singleclip_gt_bbox,

@@ -34,6 +34,37 @@ def refine_pred(model, frames, afmat, bbox, ds, mode, outidx, num_iter=2, winsiz
     return out
 
 
+def refine_pred_frames(model, frames, bbox0, outidx, num_iter=2, winsize_scale=1.50, momentum=0.8, batch_size=8):
+    """refine_pred over FULL frames: the same arithmetic, with the re-crop on the GPU (deephar_amd/frontend.py) instead of in
+    a dataset.  `frames`: one uint8 [H, W, 3] image per sample (or a frontend.FrameStore), uploaded once for all iterations;
+    `bbox0`: the initial float boxes [N, 4] -- what the dataset's `bbox` view shows before any custom box is set.  Every
+    iteration crops window crop_box(*bbox_to_objposwin(box)) like the loader does (mpii.py:102-115), unflipped.  Returns
+    the list of per-iteration poses in image coordinates."""
+    from .. import frontend
+    if not isinstance(frames, frontend.FrameStore) and hasattr(model, 'executor'):
+        frames = frontend.FrameStore(frames, model.executor.device)
+    index = np.arange(len(bbox0))
+    current = np.array(bbox0, dtype=np.float64).copy()
+    out = []
+    for t in range(num_iter):
+        windows = np.stack([frontend.crop_box(*bbox_to_objposwin(b)) for b in current])
+        res = frontend.predict_from_frames(model, frames, index, windows, batch_size=batch_size)
+        pred, A = res[outidx], res[-1]
+        pred = transform_pose_sequence(A.copy(), pred, inverse=True)
+        out.append(pred)
+        if t == num_iter - 1:
+            break
+        refined = current.copy()
+        lo, hi = pred[:, :, 0:2].min(axis=1), pred[:, :, 0:2].max(axis=1)
+        for i in range(len(pred)):
+            centre_p = np.array([(lo[i, 0] + hi[i, 0]) / 2, (lo[i, 1] + hi[i, 1]) / 2])
+            side = winsize_scale * max(hi[i, 0] - lo[i, 0], hi[i, 1] - lo[i, 1])
+            centre_t, _ = bbox_to_objposwin(current[i])
+            refined[i, :] = objposwin_to_bbox(momentum * centre_t + (1 - momentum) * centre_p, (side, side))
+        current = refined
+    return out
+
+
 def get_bbox_from_poses(poses, afmat, scale=1.5):
     """One box (image coordinates) around all confident joints (> 0.25) of a batch of predicted poses
     [N, J, >=3] or of the first clip of [1, T, J, >=3]; the confidence is read from channel -2 like the

@@ -1,0 +1,157 @@
+"""Crop-and-resize front end: predict from FULL frames and boxes.
+
+The reference crops on the host with PIL, per frame and per call -- T.rotate_crop(angle, objpos, winsize), T.resize(
+crop_resolution), optional T.horizontal_flip() (deephar/data/mpii.py:114-118, pennaction.py:157-161) -- and callers such as
+the box-refinement loop (exp/common/mpii_tools.py:13-52) re-crop the same images again and again.  Here the frames are
+uploaded once (FrameStore) and every chunk's crops are ONE launch (dh_crop_resize_u8) that writes straight into the uint8
+input of the bound plan; the result is bit for bit `model.predict(<the loader's uint8 crops>)`.
+
+Scope: the loaders' test-mode geometry -- angle 0, integer window, bilinear, optional mirror, 3 channels, uint8.  Box and
+matrix bookkeeping stays on the host in float64 (crop_box, crop_afmat), composed like deephar/utils/transform.py does.
+The reference pins Pillow 5.1.0; bit-equality was checked against the Pillow recorded in tests/golden/crop_reference.npz.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def crop_box(objpos, winsize):
+    """The integer window of T.rotate_crop(0, objpos, winsize) (transform.py:110-111): corners truncated toward zero."""
+    cx, cy = float(objpos[0]), float(objpos[1])
+    w, h = float(winsize[0]), float(winsize[1])
+    return np.array([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], dtype=int)
+
+
+def crop_afmat(box, out_wh, hflip=False):
+    """afmat of the loaders after crop, resize, optional flip and normalize_affinemap: image pixels -> [0, 1] crop coordinates.
+    Composed by np.dot(t, afmat) in the loaders' order, one elementary matrix at a time, so every entry has their bits."""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    ow, oh = int(out_wh[0]), int(out_wh[1])
+
+    def translate(x, y):
+        t = np.eye(3)
+        t[0, 2], t[1, 2] = x, y
+        return t
+
+    def scale(w, h):
+        t = np.eye(3)
+        t[0, 0] *= w
+        t[1, 1] *= h
+        return t
+
+    A = np.dot(translate(-x0, -y0), np.eye(3))
+    A = np.dot(scale(ow / (x1 - x0), oh / (y1 - y0)), A)
+    if hflip:
+        A = np.dot(scale(-1, 1), A)
+        A = np.dot(translate(ow, 0), A)
+    return np.dot(scale(1 / ow, 1 / oh), A)
+
+
+class FrameStore:
+    """Full frames resident on the device: each uint8 [H, W, 3] frame is uploaded once; frames may differ in size."""
+
+    def __init__(self, frames, device=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise _lib.DeepharHipError('no HIP device visible: the crop front end runs only on the GPU')
+        self.device = torch.device(device or 'cuda:%d' % torch.cuda.current_device())
+        self.tensors = []
+        for f in frames:
+            a = np.ascontiguousarray(f)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError('frames must be uint8 [H, W, 3] arrays, got %s %s' % (a.dtype, a.shape))
+            self.tensors.append(torch.from_numpy(a).to(self.device))
+        torch.cuda.synchronize(self.device)          # once, at upload: every later launch may read the frames on any stream
+        self.srcs = (_lib.CropSrc * len(self.tensors))(*[
+            _lib.CropSrc(t.data_ptr(), 3 * t.shape[1], t.shape[0], t.shape[1]) for t in self.tensors])
+
+    def __len__(self):
+        return len(self.tensors)
+
+
+class CropFeed:
+    """What Executor.run_pipelined needs to crop its own input: the per-chunk crop programs over a FrameStore."""
+
+    def __init__(self, store, index, boxes, hflip, out_hw):
+        self.store, self.lib = store, _lib.load()
+        self.index = np.asarray(index, np.int64)
+        self.boxes = np.asarray(boxes, np.int64)
+        self.hflip = np.asarray(hflip).astype(bool)
+        self.OH, self.OW = int(out_hw[0]), int(out_hw[1])
+        self.total = self.index.shape[0]
+        self.per_item = int(np.prod(self.index.shape[1:], dtype=np.int64))           # frames per item: 1, or T of a clip model
+        if self.boxes.shape != self.index.shape + (4,) or self.hflip.shape != self.index.shape:
+            raise ValueError('index %s, boxes %s and hflip %s do not describe the same jobs' %
+                             (self.index.shape, self.boxes.shape, self.hflip.shape))
+        if self.total and (self.index.min() < 0 or self.index.max() >= len(store)):
+            raise ValueError('frame index outside the %d stored frames' % len(store))
+        if np.any(self.boxes[..., 2] <= self.boxes[..., 0]) or np.any(self.boxes[..., 3] <= self.boxes[..., 1]):
+            raise ValueError('empty crop box')
+        flat = np.concatenate([self.index.reshape(-1, 1), self.boxes.reshape(-1, 4), self.hflip.reshape(-1, 1)], axis=1)
+        self.jobs = np.ascontiguousarray(flat.astype(np.int32))                       # == dh_crop_job[total * per_item]
+
+    def _jobs(self, start, m):
+        part = self.jobs[start * self.per_item:(start + m) * self.per_item]
+        return part.ctypes.data_as(C.POINTER(_lib.CropJob)), len(part)
+
+    def program_bytes(self, start, m):
+        jobs, n = self._jobs(start, m)
+        nbytes = C.c_size_t(0)
+        rc = self.lib.dh_crop_program_bytes(jobs, n, len(self.store), self.OH, self.OW, C.byref(nbytes))
+        if rc == -2:
+            raise ValueError('a crop window is more than 16 times its output on one axis (or the output row does not fit LDS)')
+        _lib.check(rc, 'dh_crop_program_bytes')
+        return nbytes.value
+
+    def build(self, start, m, out):
+        """The program of items [start, start + m) into the pinned uint8 tensor `out`; returns its bytes."""
+        nbytes = self.program_bytes(start, m)
+        jobs, n = self._jobs(start, m)
+        if out.numel() < nbytes or out.data_ptr() % 8:
+            raise ValueError('crop program buffer too small or misaligned')
+        _lib.check(self.lib.dh_crop_program_build_host(self.store.srcs, len(self.store), jobs, n, self.OH, self.OW,
+                                                       out.data_ptr(), nbytes), 'dh_crop_program_build_host')
+        return nbytes
+
+
+def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32):
+    """model.predict on crops of full frames, cropped on the GPU.
+
+    frames : a FrameStore, or a sequence of uint8 [H, W, 3] arrays (uploaded once, here)
+    index  : [N] frame numbers, or [N, T] for a clip model
+    boxes  : integer windows (x0, y0, x1, y1) as crop_box makes them: [N, 4], [N, T, 4], or [N, 4] for a clip model (the
+             clip-level box is broadcast over the clip's frames)
+    hflip  : None, one flag, or one per item ([N]) or per frame ([N, T])
+    Returns the outputs of model.predict as a list, followed by the float64 affine maps [N(, T), 3, 3] (crop_afmat).
+    Bit for bit model.predict(<uint8 crops of the loader>, batch_size)."""
+    if len(model.inputs) != 1:
+        raise ValueError('predict_from_frames needs a model with a single image input, %s has %d inputs' %
+                         (model.name, len(model.inputs)))
+    shape = tuple(model.inputs[0].shape)
+    if len(shape) not in (3, 4) or shape[-1] != 3:
+        raise ValueError('predict_from_frames needs an image input [(T,) H, W, 3], the model takes %s' % (shape,))
+    index = np.asarray(index, np.int64)
+    boxes = np.asarray(boxes)
+    if boxes.dtype.kind not in 'iu':
+        raise ValueError('boxes must be integer windows (frontend.crop_box)')
+    if index.ndim != len(shape) - 2 or (len(shape) == 4 and index.shape[1] != shape[0]):
+        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, shape))
+    if len(shape) == 4 and boxes.ndim == 2:
+        boxes = np.broadcast_to(boxes[:, None, :], index.shape + (4,))
+    flips = np.zeros(index.shape, bool) if hflip is None else np.asarray(hflip).astype(bool)
+    if flips.ndim < index.ndim:
+        flips = np.broadcast_to(flips.reshape(flips.shape + (1,) * (index.ndim - flips.ndim)), index.shape)
+    OH, OW = shape[-3], shape[-2]
+    afmat = np.zeros(index.shape + (3, 3))
+    for pos in np.ndindex(*index.shape):
+        afmat[pos] = crop_afmat(boxes[pos], (OW, OH), bool(flips[pos]))
+    if index.shape[0] == 0:
+        return [np.zeros((0,) + tuple(t.shape), np.float32) for t in model.outputs] + [afmat]
+    ex = model.executor
+    store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
+    feed = CropFeed(store, index, boxes, flips, (OH, OW))
+    bs = int(min(batch_size or feed.total, feed.total))
+    outs = ex.run_pipelined(None, bs, u8_norm=model.channel_power, crop=feed)
+    return list(outs) + [afmat]

@@ -143,6 +143,50 @@ def normalize_u8(x, lut):
     return y
 
 
+def crop_resize(sources, jobs, out_hw, out=None, item_pitch=None):
+    """Crop-and-resize front end (dh_crop_resize_u8): every job in one launch on torch's current stream.
+    sources: uint8 CUDA tensors [H, W, 3], rows contiguous (a row pitch above 3 W is fine: a column slice of a wider
+    image); jobs: (source index, (x0, y0, x1, y1), hflip); out_hw = (OH, OW).  Returns uint8 [len(jobs), OH, OW, 3], bit for
+    bit PIL's Image.crop(box).resize((OW, OH), BILINEAR) [mirrored].  `out`: a flat uint8 CUDA tensor to write into, item j
+    at byte j * item_pitch (the op then returns `out`).  ValueError for a window more than 16 times its output."""
+    torch = _t()
+    lib = _lib.load()
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    srcs = (_lib.CropSrc * len(sources))()
+    for i, s in enumerate(sources):
+        if not (s.is_cuda and s.dtype == torch.uint8 and s.dim() == 3 and s.shape[2] == 3 and s.stride(2) == 1 and s.stride(1) == 3):
+            raise ValueError('crop_resize expects uint8 CUDA tensors [H, W, 3] with contiguous rows')
+        srcs[i] = _lib.CropSrc(s.data_ptr(), s.stride(0), s.shape[0], s.shape[1])
+    cj = (_lib.CropJob * len(jobs))(*[_lib.CropJob(int(s), int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(bool(f)))
+                                      for s, b, f in jobs])
+    nbytes = C.c_size_t(0)
+    rc = lib.dh_crop_program_bytes(cj, len(jobs), len(sources), OH, OW, C.byref(nbytes))
+    if rc == 0:
+        prog = torch.empty(nbytes.value, dtype=torch.uint8, pin_memory=True)
+        rc = lib.dh_crop_program_build_host(srcs, len(sources), cj, len(jobs), OH, OW, prog.data_ptr(), nbytes.value)
+    if rc == -2:
+        raise ValueError('crop_resize: a window is more than 16 times its output on one axis, or the output is too wide')
+    if rc == -1:
+        raise ValueError('crop_resize: bad argument (empty box, source index, row pitch below 3 W)')
+    _lib.check(rc, 'dh_crop_program_build_host')
+    device = sources[0].device
+    prog_dev = prog.to(device, non_blocking=True)
+    if out is None:
+        item_pitch = OH * OW * 3
+        y = torch.empty((len(jobs), OH, OW, 3), dtype=torch.uint8, device=device)
+    else:
+        y = out
+        if not (y.is_cuda and y.dtype == torch.uint8 and y.is_contiguous()) or item_pitch is None or \
+                y.numel() < (len(jobs) - 1) * item_pitch + OH * OW * 3:
+            raise ValueError('crop_resize: `out` must be a contiguous uint8 CUDA tensor holding every item at item_pitch')
+    rc = lib.dh_crop_resize_u8(prog_dev.data_ptr(), len(jobs), OH, OW, y.data_ptr(), item_pitch, _stream())
+    if rc == -2:
+        raise ValueError('crop_resize: output rows of %d pixels do not fit the kernel' % OW)
+    _lib.check(rc, 'dh_crop_resize_u8')
+    prog_dev.record_stream(torch.cuda.current_stream())     # the launch reads the program after this function returns
+    return y
+
+
 def dwconv2d(x, dw_kernel, pre_scale=None, pre_shift=None, pre_relu=False, up_in=False):
     """Depthwise conv, stride 1, TF-SAME.  dw_kernel numpy [kh,kw,C,1].  up_in: x is at half resolution and the
     convolution runs on UpSampling2D((2, 2))(x) without writing it out (dh_dw_args.up_in)."""

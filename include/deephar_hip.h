@@ -635,6 +635,47 @@ int64_t dh_clip_frame_items(const dh_clip* clip);           /* elements per clip
 int dh_clip_input_is_u8(const dh_clip* clip);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Crop-and-resize front end: full frames + integer boxes in, the network's uint8 input out, in ONE launch per chunk.
+ * Replaces the TEST-MODE crop of the reference's loaders -- T.rotate_crop(0, objpos, winsize), T.resize(crop_resolution),
+ * optional T.horizontal_flip() (deephar/utils/transform.py:56-120 as deephar/data/mpii.py:114-118 and pennaction.py:157-161
+ * call it), i.e. PIL's Image.crop(box).resize(size, BILINEAR) [.transpose(FLIP_LEFT_RIGHT)] on 8-bit RGB -- bit for bit:
+ * PIL's 8-bit resize is integer arithmetic on fixed-point coefficients, restated in csrc/crop_index.h.
+ *   crop   : C[y, x] = S[y0 + y, x0 + x] inside the image, 0 outside; cw = x1 - x0, ch = y1 - y0.
+ *   axis   : (in, out) = (cw, OW) or (ch, OH), all in double ON THE HOST: scale = in / out, fs = max(scale, 1), support = fs,
+ *            ss = 1 / fs; output i: center = (i + 0.5) * scale, xmin = max(0, (int)(center - support + 0.5)),
+ *            xmax = min(in, (int)(center + support + 0.5)), w_j = max(0, 1 - |(j + xmin - center + 0.5) * ss|) normalised by
+ *            their sum, k_j = (int)(0.5 + w_j * 2^22).
+ *   passes : horizontal, then vertical: out = clip_0_255((2^21 + sum_j k_j * in[xmin + j]) >> 22); the horizontal result is
+ *            rounded to uint8 before the vertical pass reads it (it lives in LDS, never in memory); int32 accumulators.
+ *   flip   : hflip reverses the columns of the result.
+ * Scope: angle 0, integer window, bilinear, 3 channels, uint8; per-axis down-scaling up to 16 (33 taps), any up-scaling.
+ * Rotation, random augmentation and file decoding stay with the caller.  The reference pins Pillow 5.1.0; the fixtures of
+ * the tests were produced with the Pillow they record (12.2.0) -- equality with 5.1.0 itself is not verified.
+ * A CROP PROGRAM is one contiguous table the host builds and the launch reads: the source descriptors, the jobs, and per job
+ * both axes' first / count / k tables (layout: csrc/crop_index.h).  The size query answers its bytes, the builder fills HOST
+ * memory (8-byte aligned) that the caller copies to the device as it likes; the sources' `ptr` are the addresses the READER
+ * will use (device pointers for the launch, host pointers for the host twin).  Output item j (job j) is [OH, OW, 3] bytes at
+ * y + j * item_pitch.  One work-group owns a band of output rows of one job; rows move 16 bytes per lane when 3 * OW, y and
+ * item_pitch are multiples of 16 (a 256 x 3 row is), one byte per lane otherwise.  No atomics.  Nothing allocates, nothing
+ * synchronises.  DH_EINVAL: NULL pointer, empty box, pitch < 3 * W, item_pitch < OH * OW * 3, a malformed program (builder
+ * and host twin; the launch cannot read device memory and trusts what the builder wrote).  DH_EUNSUPPORTED: a window beyond
+ * the scale cap, or an output so wide that the rows one output row reads do not fit LDS -- answered by the size query, the
+ * builder and the host twin, which then write nothing.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_crop_src { const uint8_t* ptr; int64_t pitch; /* bytes between rows, >= 3 * W */ int32_t H, W; } dh_crop_src;
+typedef struct dh_crop_job { int32_t src; int32_t x0, y0, x1, y1; /* window [x0, x1) x [y0, y1), may leave the image */
+                             int32_t hflip; } dh_crop_job;
+int dh_crop_program_bytes(const dh_crop_job* jobs, int njobs, int nsrc, int OH, int OW, size_t* bytes);
+int dh_crop_program_build_host(const dh_crop_src* srcs, int nsrc, const dh_crop_job* jobs, int njobs, int OH, int OW,
+                               void* program_host, size_t bytes);
+int dh_crop_resize_u8(const void* program_dev, int njobs, int OH, int OW, uint8_t* y, int64_t item_pitch, void* stream);
+int dh_crop_resize_host(const void* program_host, size_t bytes, int njobs, int OH, int OW, uint8_t* y, int64_t item_pitch);
+/* one axis on its own (what the builder writes per job and axis): taps per output row of k, and the three tables
+ * first[out], count[out], k[out * taps] with taps >= dh_crop_axis_taps(in, out) */
+int dh_crop_axis_taps(int in, int out);
+int dh_crop_axis_coeffs_host(int in, int out, int taps, int32_t* first, int32_t* count, int32_t* k);
+
+/* ---------------------------------------------------------------------------------------------------
  * Stream-ordered runtime helpers (no torch types): graphs for launch-bound replay, events for timing.
  * ------------------------------------------------------------------------------------------------- */
 int dh_graph_begin_capture(void* stream);
