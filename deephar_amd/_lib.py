@@ -187,6 +187,15 @@ SIGNATURES = {
     'dh_crop_resize_host': (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, i64]),
     'dh_crop_axis_taps': (C.c_int, [C.c_int, C.c_int]),
     'dh_crop_axis_coeffs_host': (C.c_int, [C.c_int] * 3 + [C.POINTER(i32)] * 3),
+    'dh_crop_program_max_bytes': (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    'dh_crop_program_build_dev': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]),
+    'dh_frames_create': (C.c_int, [C.POINTER(CropSrc), C.c_int, C.POINTER(vp)]),
+    'dh_frames_destroy': (C.c_int, [vp]),
+    'dh_frames_count': (C.c_int, [vp]),
+    'dh_frames_table_dev': (vp, [vp]),
+    'dh_forward_frames_shape': (C.c_int, [C.c_int, C.c_int, i64] + [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2),
+    'dh_forward_frames': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), vp]),
+    'dh_forward_frames_host': (C.c_int, [vp, vp, C.POINTER(CropJob), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
     'dh_sched_build_ops':(C.c_int, [C.c_int] + [C.POINTER(i32)] * 5 + [C.c_int] * 4 + [C.POINTER(SchedOp), C.c_int,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dh_unpack_cut_f32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int, vp]),

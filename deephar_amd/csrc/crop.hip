@@ -1,6 +1,6 @@
 // dh_crop_resize_u8: every crop of a chunk -- window out of a full frame, PIL's 8-bit bilinear resize, optional mirror -- in
 // ONE launch, written straight into the network's uint8 input.  Integer arithmetic only: the coefficients arrive in the crop
-// program (crop_index.h), computed in double on the host.
+// program (crop_index.h), computed in double by a builder -- on the host, or on the device (below).
 //   grid (njobs, ceil(OH / kCropGroupRows)): work-group (j, g) walks the bands g, g + gridDim.y, ... of job j; a band is
 //   `band` output rows (chosen by the builder from the job's vertical scale so that the rows it reads fit LDS).
 //   pass 1: the source rows the band's vertical taps need, one lane per (row, output column), lanes along the row; clipped to
@@ -8,6 +8,15 @@
 //   pass 2: the vertical pass from LDS, 16 output bytes per lane (LDS rows are 16-byte multiples apart), stored as one 16-byte
 //           vector store, or one byte per lane when the row length or the destination does not allow it.
 // The intermediate never reaches memory.  No atomics.  The index arithmetic is shared with the host twin dh_crop_resize_host.
+//
+// dh_crop_program_build_dev: the crop program itself built on the device from a job table in device memory -- byte for byte
+// what crop_program_build (crop_index.h) writes on the host -- as two small launches:
+//   layout: ONE work-group.  Lane t validates jobs t, t + 256, ..., takes their tap counts and table bytes; an exclusive scan
+//           over the work-group with a running carry from chunk to chunk of 256 jobs gives every job its two table offsets;
+//           then the header, the source table and every job record are written.  A job that fails a check gets a record
+//           with band = 0 (crop_resize_kernel skips it), no table bytes, and its code in status[j].
+//   tables: grid (njobs, 2): work-group (j, 0) fills the x table of job j, (j, 1) the y table, one lane per output index
+//           (crop_axis_output: the host's doubles, contraction off); (j, 1) then picks the job's band from its finished table.
 #include "dh_kernels.h"
 #include "crop_index.h"
 
@@ -87,6 +96,109 @@ __global__ __launch_bounds__(kCropThreads) void crop_resize_kernel(const uint8_t
   }
 }
 
+// ---- the program builder --------------------------------------------------------------------------------------------------
+// DH_OK, or why job g cannot run: the host builder's checks in its order, per job (a bad source fails only the jobs naming it)
+__device__ inline int crop_job_status(const dh_crop_job& g, const dh_crop_src* srcs, int nsrc, int OH, int OW) {
+  if (!crop_job_ok(g, nsrc)) return DH_EINVAL;
+  if (!crop_axis_supported(g.x1 - g.x0, OW) || !crop_axis_supported(g.y1 - g.y0, OH)) return DH_EUNSUPPORTED;
+  if (!crop_src_ok(srcs[g.src])) return DH_EINVAL;
+  return DH_OK;
+}
+
+__global__ __launch_bounds__(kCropThreads) void crop_layout_kernel(const dh_crop_src* __restrict__ srcs, int nsrc,
+                                                                    const dh_crop_job* __restrict__ jobs, int njobs, int OH, int OW,
+                                                                    uint8_t* __restrict__ prog, int32_t* __restrict__ status) {
+  __shared__ uint32_t scan[kCropThreads];
+  const int tid = threadIdx.x;
+  const uint32_t src_off = (uint32_t)sizeof(CropHeader);
+  const uint32_t job_off = src_off + (uint32_t)nsrc * (uint32_t)sizeof(dh_crop_src);
+  uint32_t carry = job_off + (uint32_t)njobs * (uint32_t)sizeof(CropJobRec);     // where the next chunk's first table starts
+  CropJobRec* recs = reinterpret_cast<CropJobRec*>(prog + job_off);
+  for (int base = 0; base < njobs; base += kCropThreads) {                       // (uniform: every lane runs every chunk)
+    const int j = base + tid;
+    CropJobRec r = {};
+    uint32_t xbytes = 0, ybytes = 0;
+    int rc = DH_OK;
+    if (j < njobs) {
+      const dh_crop_job g = jobs[j];
+      rc = crop_job_status(g, srcs, nsrc, OH, OW);
+      r.src = g.src; r.x0 = g.x0; r.y0 = g.y0; r.x1 = g.x1; r.y1 = g.y1; r.hflip = g.hflip ? 1 : 0;
+      if (rc == DH_OK) {
+        r.xtaps = crop_axis_taps(g.x1 - g.x0, OW);
+        r.ytaps = crop_axis_taps(g.y1 - g.y0, OH);
+        xbytes = (uint32_t)crop_axis_table_bytes(OW, r.xtaps);
+        ybytes = (uint32_t)crop_axis_table_bytes(OH, r.ytaps);
+      }
+    }
+    // inclusive scan of the chunk's table bytes (the host refused a program above 2^31 - 1 bytes: no sum wraps)
+    scan[tid] = xbytes + ybytes;
+    __syncthreads();
+    for (int d = 1; d < kCropThreads; d <<= 1) {
+      const uint32_t below = tid >= d ? scan[tid - d] : 0u;
+      __syncthreads();
+      scan[tid] += below;
+      __syncthreads();
+    }
+    if (j < njobs) {
+      if (rc == DH_OK) {
+        r.xtab = carry + scan[tid] - (xbytes + ybytes);
+        r.ytab = r.xtab + xbytes;
+      }
+      recs[j] = r;                                 // band = 0 until the y table's work-group has picked it (never, for a refused job)
+      if (status != nullptr) status[j] = rc;
+    }
+    carry += scan[kCropThreads - 1];
+    __syncthreads();                               // the next chunk overwrites scan[]
+  }
+  if (tid == 0) {
+    const CropHeader h = {kCropMagic, nsrc, njobs, OH, OW, src_off, job_off, carry};
+    *reinterpret_cast<CropHeader*>(prog) = h;
+  }
+  // the source table, 8 bytes per lane (both tables are 8-byte aligned, a descriptor is 24 bytes)
+  const uint64_t* s8 = reinterpret_cast<const uint64_t*>(srcs);
+  uint64_t* d8 = reinterpret_cast<uint64_t*>(prog + src_off);
+  for (int i = tid; i < nsrc * 3; i += kCropThreads) d8[i] = s8[i];
+}
+
+__global__ __launch_bounds__(kCropThreads) void crop_tables_kernel(uint8_t* __restrict__ prog, int njobs, int OH, int OW) {
+  __shared__ int too_big[5];                       // per band candidate 16, 8, 4, 2, 1: some fill of LDS does not fit
+  const int tid = threadIdx.x, j = blockIdx.x, yaxis = blockIdx.y;
+  const CropHeader h = *reinterpret_cast<const CropHeader*>(prog);
+  if (h.magic != kCropMagic || j >= njobs || j >= h.njobs) return;                                   // (uniform)
+  CropJobRec* rec = reinterpret_cast<CropJobRec*>(prog + h.job_off) + j;
+  const CropJobRec r = *rec;
+  if (r.xtaps < 1 || r.ytaps < 1) return;                                                            // a refused job: no tables
+  const int in = yaxis ? r.y1 - r.y0 : r.x1 - r.x0, out = yaxis ? OH : OW, taps = yaxis ? r.ytaps : r.xtaps;
+  int32_t* tab = reinterpret_cast<int32_t*>(prog + (yaxis ? r.ytab : r.xtab));
+  const CropAxis ax = crop_axis_setup(in, out);
+  for (int i = tid; i < out; i += kCropThreads) crop_axis_output(ax, in, taps, i, tab, tab + out, tab + 2 * (size_t)out);
+  if (tid == 0 && crop_axis_table_pad(out, taps)) tab[(size_t)out * (2 + (size_t)taps)] = 0;
+  if (!yaxis) return;
+  // The band, from the finished y table.  first / count are walked from GLOBAL memory (an LDS copy would need up to
+  // 2 * kCropMaxExtent ints): the barrier below carries the work-group-scope fence that makes this work-group's table stores
+  // visible to its own lanes; nobody else reads them before the launch ends.
+  if (tid < 5) too_big[tid] = 0;
+  __threadfence_block();
+  __syncthreads();
+  const int32_t* yfirst = tab;
+  const int32_t* ycount = tab + OH;
+  const int pitch = crop_lds_pitch(OW);
+  for (int b = 0; b < 5; ++b) {                    // crop_pick_band's test, the fills of a candidate dealt to the lanes
+    const int band = kCropMaxBand >> b;
+    for (int64_t r0 = (int64_t)tid * band; r0 < OH; r0 += (int64_t)kCropThreads * band) {
+      const int r1 = r0 + band < OH ? (int)r0 + band : OH;
+      if ((int64_t)crop_band_rows(yfirst, ycount, (int)r0, r1) * pitch > kCropLdsBytes) too_big[b] = 1;   // (same value from every lane)
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int band = 0;
+    for (int b = 4; b >= 0; --b)
+      if (!too_big[b]) band = kCropMaxBand >> b;
+    rec->band = band;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -109,6 +221,33 @@ int dh_crop_program_bytes(const dh_crop_job* jobs, int njobs, int nsrc, int OH, 
 int dh_crop_program_build_host(const dh_crop_src* srcs, int nsrc, const dh_crop_job* jobs, int njobs, int OH, int OW,
                                void* program_host, size_t bytes) {
   return dh::crop_program_build(srcs, nsrc, jobs, njobs, OH, OW, program_host, bytes);
+}
+
+int dh_crop_program_max_bytes(int njobs, int nsrc, int OH, int OW, size_t* bytes) {
+  const size_t n = dh::crop_program_max_bytes(njobs, nsrc, OH, OW);
+  if (bytes == nullptr || n == 0) return DH_EINVAL;
+  if (n > 0x7fffffffu) return DH_EUNSUPPORTED;                       // offsets inside a program are 32 bits, like the size query says
+  *bytes = n;
+  return DH_OK;
+}
+
+int dh_crop_program_build_dev(const dh_crop_src* srcs_dev, int nsrc, const dh_crop_job* jobs_dev, int njobs, int OH, int OW,
+                              void* program_dev, size_t capacity, int32_t* status_dev, void* stream) {
+  size_t need = 0;
+  const int rc = dh_crop_program_max_bytes(njobs, nsrc, OH, OW, &need);
+  if (rc != DH_OK) return rc;
+  if (srcs_dev == nullptr || jobs_dev == nullptr || program_dev == nullptr || ((uintptr_t)program_dev & 7) != 0 ||
+      ((uintptr_t)srcs_dev & 7) != 0 || ((uintptr_t)jobs_dev & 3) != 0 || ((uintptr_t)status_dev & 3) != 0 || capacity < need)
+    return DH_EINVAL;
+  // the host builder's last refusal, for the worst job the table may hold: one output row reads at most kCropMaxTaps rows
+  if ((int64_t)dh::kCropMaxTaps * dh::crop_lds_pitch(OW) > dh::kCropLdsBytes) return DH_EUNSUPPORTED;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint8_t* prog = static_cast<uint8_t*>(program_dev);
+  hipLaunchKernelGGL(crop_layout_kernel, dim3(1), dim3(dh::kCropThreads), 0, s, srcs_dev, nsrc, jobs_dev, njobs, OH, OW, prog, status_dev);
+  int lrc = dh::check_launch();
+  if (lrc != DH_OK) return lrc;
+  hipLaunchKernelGGL(crop_tables_kernel, dim3((unsigned)njobs, 2u), dim3(dh::kCropThreads), 0, s, prog, njobs, OH, OW);
+  return dh::check_launch();
 }
 
 int dh_crop_resize_host(const void* program_host, size_t bytes, int njobs, int OH, int OW, uint8_t* y, int64_t item_pitch) {

@@ -1,12 +1,18 @@
 // The arithmetic of the crop-and-resize front end (dh_crop_resize_u8, crop.hip) as pure functions: the fixed-point resampling
 // coefficients of one axis (PIL's 8-bit bilinear resize restated: Image.crop(box).resize(size, BILINEAR), which is what the
 // reference's loaders run per frame -- deephar/data/mpii.py:114-115, pennaction.py:157-158), the tap bound, the clipping of a
-// crop window against its image, and the layout of a CROP PROGRAM: one contiguous table the host builds and a launch reads.
-// No HIP header, no stream.  The kernel, the host twin dh_crop_resize_host, tools/crop_sweep.cpp and the host tests use these.
+// crop window against its image, and the layout of a CROP PROGRAM: one contiguous table a builder writes and a launch reads.
+// No HIP header, no stream.  The kernels, the host twin dh_crop_resize_host, tools/crop_sweep.cpp and the host tests use these.
 //
-// Every `double` below runs on the HOST only (crop_axis_coeffs and what calls it are not device functions): the device sees
-// integers, so no contraction on the device can change a coefficient.  On the host the two products that feed an addition go
-// through a volatile, so a compiler that targets an FMA unit cannot fuse them either.
+// The doubles below run on the host (crop_program_build) AND on the device (dh_crop_program_build_dev: one lane per output
+// index calls crop_axis_output), and both must give the same bits.  Every operation is one IEEE double operation -- in / out,
+// 1 / fs, the centre, the triangle weights summed in ascending j, w / ww, 0.5 + v * 2^22 -- so the only hazard is CONTRACTION
+// of a product and the addition it feeds into one fused multiply-add:
+//   clang (hipcc, host and device passes): `#pragma clang fp contract(off)` in every function that holds such a pair.  On
+//     gfx950 the only v_fma_f64 left are those of the division expansions, which are the correctly rounded quotient (the
+//     build has no fast-math flag, and must not get one: an approximate fp64 division would change coefficients).
+//   other host compilers: the two products that feed an addition go through a volatile.  Not on the device, where a volatile
+//     local costs scratch memory.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -31,9 +37,20 @@ constexpr int kCropGroupRows = 8;                 // the grid has ceil(OH / 8) w
 constexpr uint32_t kCropMagic = 0x50524344u;      // "DCRP"
 constexpr int kCropMaxExtent = 1 << 20;           // image / window / output extents: offsets stay far inside 32 bits per row
 
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DH_CROP_NOFUSE
+#else
+#define DH_CROP_NOFUSE volatile
+#endif
+#if defined(__clang__)
+#define DH_CROP_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define DH_CROP_NO_CONTRACT
+#endif
+
 // ---- one axis --------------------------------------------------------------------------------------------------------------
 // taps an output of this axis can have: PIL's ksize = (int)ceil(support) * 2 + 1 with support = max(in / out, 1)
-inline int crop_axis_taps(int in, int out) {
+DH_CROP_HD inline int crop_axis_taps(int in, int out) {
   const double scale = (double)in / (double)out;
   const double support = scale < 1.0 ? 1.0 : scale;
   int c = (int)support;
@@ -41,40 +58,56 @@ inline int crop_axis_taps(int in, int out) {
   return 2 * c + 1;
 }
 // scale <= 16 without a division: in <= 16 * out
-inline bool crop_axis_supported(int in, int out) { return (int64_t)in <= (int64_t)kCropMaxScale * out; }
+DH_CROP_HD inline bool crop_axis_supported(int in, int out) { return (int64_t)in <= (int64_t)kCropMaxScale * out; }
 
-// first[i], count[i], k[i * taps + j]: output i reads input first[i] + j with weight k / 2^22 for j < count[i]; the slots behind
-// count[i] are 0.  `taps` >= crop_axis_taps(in, out).
-inline void crop_axis_coeffs(int in, int out, int taps, int32_t* first, int32_t* count, int32_t* k) {
-  const double scale = (double)in / (double)out;
-  const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = fs;
-  const double ss = 1.0 / fs;
-  for (int i = 0; i < out; ++i) {
-    volatile double center = ((double)i + 0.5) * scale;
-    const double c = center;
-    int xmin = (int)(c - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(c + support + 0.5);
-    if (xmax > in) xmax = in;
-    int n = xmax - xmin;
-    if (n > taps) n = taps;                       // never with taps >= crop_axis_taps
-    const auto weight = [&](int j) {             // the same double every time it is asked: no scratch array, any tap count
-      volatile double p = ((double)(j + xmin) - c + 0.5) * ss;
-      double a = p;
-      if (a < 0.0) a = -a;
-      return a < 1.0 ? 1.0 - a : 0.0;
-    };
-    double ww = 0.0;
-    for (int j = 0; j < n; ++j) ww += weight(j);
-    first[i] = xmin;
-    count[i] = n;
-    for (int j = 0; j < n; ++j) {
-      const double v = ww != 0.0 ? weight(j) / ww : weight(j);
-      k[(size_t)i * taps + j] = (int32_t)(0.5 + v * (double)(1 << kCropPrecisionBits));
-    }
-    for (int j = n; j < taps; ++j) k[(size_t)i * taps + j] = 0;
+// what every output of an axis shares: scale = in / out, support = max(scale, 1), ss = 1 / support
+struct CropAxis {
+  double scale, support, ss;
+};
+DH_CROP_HD inline CropAxis crop_axis_setup(int in, int out) {
+  CropAxis a;
+  a.scale = (double)in / (double)out;
+  a.support = a.scale < 1.0 ? 1.0 : a.scale;
+  a.ss = 1.0 / a.support;
+  return a;
+}
+// the triangle weight of input x for an output centred at c: the same double every time it is asked
+DH_CROP_HD inline double crop_axis_weight(int x, double c, double ss) {
+  DH_CROP_NO_CONTRACT
+  DH_CROP_NOFUSE double p = ((double)x - c + 0.5) * ss;
+  double a = p;
+  if (a < 0.0) a = -a;
+  return a < 1.0 ? 1.0 - a : 0.0;
+}
+// ONE output index i of an axis: first[i], count[i], k[i * taps + j] -- output i reads input first[i] + j with weight
+// k / 2^22 for j < count[i]; the slots behind count[i] are 0.  `taps` >= crop_axis_taps(in, out).  Host and device: the
+// device builder runs one lane per i.  No scratch array, any tap count.
+DH_CROP_HD inline void crop_axis_output(const CropAxis& ax, int in, int taps, int i, int32_t* first, int32_t* count, int32_t* k) {
+  DH_CROP_NO_CONTRACT
+  DH_CROP_NOFUSE double center = ((double)i + 0.5) * ax.scale;
+  const double c = center;
+  int xmin = (int)(c - ax.support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(c + ax.support + 0.5);
+  if (xmax > in) xmax = in;
+  int n = xmax - xmin;
+  if (n > taps) n = taps;                         // never with taps >= crop_axis_taps
+  double ww = 0.0;
+  for (int j = 0; j < n; ++j) ww += crop_axis_weight(j + xmin, c, ax.ss);
+  first[i] = xmin;
+  count[i] = n;
+  int32_t* row = k + (size_t)i * taps;
+  for (int j = 0; j < n; ++j) {
+    const double w = crop_axis_weight(j + xmin, c, ax.ss);
+    const double v = ww != 0.0 ? w / ww : w;
+    row[j] = (int32_t)(0.5 + v * (double)(1 << kCropPrecisionBits));     // (v * 2^22 is exact: fused or not, the same double)
   }
+  for (int j = n; j < taps; ++j) row[j] = 0;
+}
+// the whole axis on the host: the loop over crop_axis_output
+inline void crop_axis_coeffs(int in, int out, int taps, int32_t* first, int32_t* count, int32_t* k) {
+  const CropAxis ax = crop_axis_setup(in, out);
+  for (int i = 0; i < out; ++i) crop_axis_output(ax, in, taps, i, first, count, k);
 }
 
 // ---- the arithmetic both passes share --------------------------------------------------------------------------------------
@@ -136,22 +169,32 @@ struct CropJobRec {
 static_assert(sizeof(CropHeader) == 32 && sizeof(CropJobRec) == 48 && sizeof(dh_crop_src) == 24 && sizeof(dh_crop_job) == 24,
               "crop program layout");
 
-inline bool crop_job_ok(const dh_crop_job& j, int nsrc) {
+DH_CROP_HD inline bool crop_job_ok(const dh_crop_job& j, int nsrc) {
   return j.src >= 0 && j.src < nsrc && j.x1 > j.x0 && j.y1 > j.y0 && j.x0 > -kCropMaxExtent && j.y0 > -kCropMaxExtent &&
          j.x1 < kCropMaxExtent && j.y1 < kCropMaxExtent && (int64_t)j.x1 - j.x0 <= kCropMaxExtent &&
          (int64_t)j.y1 - j.y0 <= kCropMaxExtent;
 }
-inline bool crop_src_ok(const dh_crop_src& s) {
+DH_CROP_HD inline bool crop_src_ok(const dh_crop_src& s) {
   return s.ptr != nullptr && s.H >= 1 && s.W >= 1 && s.H <= kCropMaxExtent && s.W <= kCropMaxExtent && s.pitch >= (int64_t)3 * s.W;
 }
-inline size_t crop_axis_table_bytes(int out, int taps) { return ((size_t)out * (2 + (size_t)taps) * 4 + 7) & ~(size_t)7; }
+DH_CROP_HD inline size_t crop_axis_table_bytes(int out, int taps) { return ((size_t)out * (2 + (size_t)taps) * 4 + 7) & ~(size_t)7; }
+// an odd `out` leaves 4 bytes between the table's last int32 and its 8-byte end: both builders write 0 there, so a program is
+// the same bytes whoever built it and whatever its buffer held
+DH_CROP_HD inline bool crop_axis_table_pad(int out, int taps) { return (((size_t)out * (2 + (size_t)taps)) & 1) != 0; }
+// What a caller allocates before the boxes are known: header + source table + job records + per job both axis tables at
+// kCropMaxTaps.  >= crop_program_bytes of every table crop_program_bytes accepts.  0: a bad argument.
+DH_CROP_HD inline size_t crop_program_max_bytes(int njobs, int nsrc, int OH, int OW) {
+  if (njobs < 1 || nsrc < 1 || OH < 1 || OW < 1 || OH > kCropMaxExtent || OW > kCropMaxExtent) return 0;
+  return sizeof(CropHeader) + (size_t)nsrc * sizeof(dh_crop_src) +
+         (size_t)njobs * (sizeof(CropJobRec) + crop_axis_table_bytes(OW, kCropMaxTaps) + crop_axis_table_bytes(OH, kCropMaxTaps));
+}
 
 // rows of the intermediate a band [r0, r1) of output rows reads
 DH_CROP_HD inline int crop_band_rows(const int32_t* yfirst, const int32_t* ycount, int r0, int r1) {
   return yfirst[r1 - 1] + ycount[r1 - 1] - yfirst[r0];
 }
 // the largest band (a power of two <= kCropMaxBand) all of whose fills fit LDS; 0: not even single rows do
-inline int crop_pick_band(const int32_t* yfirst, const int32_t* ycount, int OH, int OW) {
+DH_CROP_HD inline int crop_pick_band(const int32_t* yfirst, const int32_t* ycount, int OH, int OW) {
   const int pitch = crop_lds_pitch(OW);
   for (int band = kCropMaxBand; band >= 1; band >>= 1) {
     bool fits = true;
@@ -207,10 +250,12 @@ inline int crop_program_build(const dh_crop_src* srcs, int nsrc, const dh_crop_j
     r.xtab = (uint32_t)off;
     int32_t* xt = reinterpret_cast<int32_t*>(base + off);
     crop_axis_coeffs(cw, OW, r.xtaps, xt, xt + OW, xt + 2 * (size_t)OW);
+    if (crop_axis_table_pad(OW, r.xtaps)) xt[(size_t)OW * (2 + (size_t)r.xtaps)] = 0;
     off += crop_axis_table_bytes(OW, r.xtaps);
     r.ytab = (uint32_t)off;
     int32_t* yt = reinterpret_cast<int32_t*>(base + off);
     crop_axis_coeffs(ch, OH, r.ytaps, yt, yt + OH, yt + 2 * (size_t)OH);
+    if (crop_axis_table_pad(OH, r.ytaps)) yt[(size_t)OH * (2 + (size_t)r.ytaps)] = 0;
     off += crop_axis_table_bytes(OH, r.ytaps);
     r.band = crop_pick_band(yt, yt + OH, OH, OW);  // >= 1: a single row reads at most ytaps rows, checked above
     memcpy(base + h.job_off + (size_t)j * sizeof(CropJobRec), &r, sizeof(r));

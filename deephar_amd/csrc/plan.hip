@@ -7,10 +7,13 @@
 // blob carries the engine's multi-stream schedule: plan_sched.h (GPU-free) turns it into the enqueue program of
 // BoundPlan.launch_all, which dh_forward runs with the caller's stream as stream 0 and the plan's own side streams.  Every
 // forward ends with ONE dh_pack_outputs_f32 launch (out_pack.hip) for all wanted outputs.
+// dh_frames_* / dh_forward_frames: a uint8 plan fed from full frames and boxes -- the crop program built on the device
+// (dh_crop_program_build_dev), ONE crop launch straight into the plan's uint8 input, then the forward with its input copy skipped.
 #include <cstring>
 #include <vector>
 #include "dh_kernels.h"
 #include "plan_sched.h"
+#include "crop_index.h"
 
 namespace {
 
@@ -48,6 +51,18 @@ struct dh_plan {
   float* out_stage = nullptr;
   float* out_host = nullptr;
   hipStream_t stream = nullptr;
+  // dh_forward_frames (allocated on first use, grown when a call needs more): the device crop program; the device twin of
+  // dh_forward_frames_host's job table
+  void* crop_prog = nullptr;
+  size_t crop_prog_bytes = 0;
+  dh_crop_job* crop_jobs = nullptr;
+  size_t crop_jobs_n = 0;
+};
+
+// full frames resident on the device: dense rows (pitch 3 * W), one allocation per frame, and the source table of the launch
+struct dh_frames {
+  std::vector<uint8_t*> px;
+  dh_crop_src* table = nullptr;
 };
 
 namespace {
@@ -388,6 +403,8 @@ int dh_plan_destroy(dh_plan* pl) {
   if (pl->arena) hipFree(pl->arena);
   if (pl->weights) hipFree(pl->weights);
   if (pl->bytes) hipFree(pl->bytes);
+  if (pl->crop_prog) hipFree(pl->crop_prog);
+  if (pl->crop_jobs) hipFree(pl->crop_jobs);
   delete pl;
   return DH_OK;
 }
@@ -472,43 +489,46 @@ int dh_sched_build_ops(int n, const int32_t* step, const int32_t* stream, const 
   return DH_OK;
 }
 
-int dh_forward_host(dh_plan* pl, const float* const* inputs_host, int m, float* const* outputs_host) {
-  if (pl == nullptr || inputs_host == nullptr || outputs_host == nullptr || m <= 0 || m > pl->n) return DH_EINVAL;
-  if (pl->stream == nullptr) {
-    // staging is built in locals and committed only when every allocation succeeded: a failure part-way leaves the plan
-    // as it was (the next call tries again) instead of with short in_dev / out_dev vectors
-    hipStream_t st = nullptr;
-    std::vector<float*> in_dev;
-    float* out_stage = nullptr;
-    float* out_host = nullptr;
-    bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
-    for (size_t i = 0; ok && i < pl->ins.size(); ++i) {
-      float* q = nullptr;
-      ok = hipMalloc(&q, pl->ins[i].items * (pl->ins[i].u8 ? 1 : 4) * (size_t)pl->n) == hipSuccess;
-      if (ok) in_dev.push_back(q);
-    }
-    size_t stage = 0;                                         // floats: every output of a full batch, each from a 16-byte boundary
-    for (const Out& o : pl->outs) stage += stage_floats(o, pl->n);
-    ok = ok && hipMalloc(&out_stage, stage * 4) == hipSuccess;
-    ok = ok && hipHostMalloc(&out_host, stage * 4, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-      for (float* q : in_dev) hipFree(q);
-      if (out_stage) hipFree(out_stage);
-      if (out_host) hipHostFree(out_host);
-      if (st) hipStreamDestroy(st);
-      return DH_ELAUNCH;
-    }
-    pl->in_dev.swap(in_dev);
-    pl->out_stage = out_stage;
-    pl->out_host = out_host;
-    pl->stream = st;
+}  // extern "C"
+
+namespace {
+
+// dh_forward_host / dh_forward_frames_host: the internal stream and the staging buffers, on first use.  Built in locals and
+// committed only when every allocation succeeded: a failure part-way leaves the plan as it was (the next call tries again)
+// instead of with short in_dev / out_dev vectors
+int host_staging(dh_plan* pl) {
+  if (pl->stream != nullptr) return DH_OK;
+  hipStream_t st = nullptr;
+  std::vector<float*> in_dev;
+  float* out_stage = nullptr;
+  float* out_host = nullptr;
+  bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+  for (size_t i = 0; ok && i < pl->ins.size(); ++i) {
+    float* q = nullptr;
+    ok = hipMalloc(&q, pl->ins[i].items * (pl->ins[i].u8 ? 1 : 4) * (size_t)pl->n) == hipSuccess;
+    if (ok) in_dev.push_back(q);
   }
-  for (size_t i = 0; i < pl->ins.size(); ++i)
-    if (hipMemcpyAsync(pl->in_dev[i], inputs_host[i], pl->ins[i].items * (pl->ins[i].u8 ? 1 : 4) * (size_t)m,
-                       hipMemcpyHostToDevice, pl->stream) != hipSuccess)
-      return DH_ELAUNCH;
-  // the wanted outputs of THIS call back to back in the staging buffer (the pack launch of dh_forward writes them there),
-  // ONE device-to-host copy of exactly those floats, then a host-side scatter
+  size_t stage = 0;                                         // floats: every output of a full batch, each from a 16-byte boundary
+  for (const Out& o : pl->outs) stage += stage_floats(o, pl->n);
+  ok = ok && hipMalloc(&out_stage, stage * 4) == hipSuccess;
+  ok = ok && hipHostMalloc(&out_host, stage * 4, hipHostMallocDefault) == hipSuccess;
+  if (!ok) {
+    for (float* q : in_dev) hipFree(q);
+    if (out_stage) hipFree(out_stage);
+    if (out_host) hipHostFree(out_host);
+    if (st) hipStreamDestroy(st);
+    return DH_ELAUNCH;
+  }
+  pl->in_dev.swap(in_dev);
+  pl->out_stage = out_stage;
+  pl->out_host = out_host;
+  pl->stream = st;
+  return DH_OK;
+}
+
+// the wanted outputs of THIS call back to back in the staging buffer (the pack launch of dh_forward writes them there);
+// returns the floats used
+size_t place_outputs(dh_plan* pl, float* const* outputs_host, int m) {
   pl->out_ptr.assign(pl->outs.size(), nullptr);
   size_t used = 0;
   for (size_t i = 0; i < pl->outs.size(); ++i)
@@ -516,8 +536,11 @@ int dh_forward_host(dh_plan* pl, const float* const* inputs_host, int m, float* 
       pl->out_ptr[i] = pl->out_stage + used;
       used += stage_floats(pl->outs[i], m);
     }
-  const int rc = dh_forward(pl, pl->in_dev.data(), m, pl->out_ptr.data(), pl->stream);
-  if (rc != DH_OK) return rc;
+  return used;
+}
+
+// ONE device-to-host copy of exactly those floats, the wait, then a host-side scatter
+int fetch_outputs(dh_plan* pl, float* const* outputs_host, int m, size_t used) {
   if (used != 0 && hipMemcpyAsync(pl->out_host, pl->out_stage, used * 4, hipMemcpyDeviceToHost, pl->stream) != hipSuccess)
     return DH_ELAUNCH;
   if (hipStreamSynchronize(pl->stream) != hipSuccess) return DH_ELAUNCH;
@@ -525,6 +548,136 @@ int dh_forward_host(dh_plan* pl, const float* const* inputs_host, int m, float* 
     if (outputs_host[i] != nullptr)
       std::memcpy(outputs_host[i], pl->out_host + (pl->out_ptr[i] - pl->out_stage), pl->outs[i].npix * pl->outs[i].C * 4 * (size_t)m);
   return DH_OK;
+}
+
+// dh_forward_frames_shape of this plan: the items `njobs` crops of OH x OW x 3 bytes fill and the frames per item, or DH_EINVAL
+int frames_shape(const dh_plan* pl, int njobs, int OH, int OW, int* m, int* per_item) {
+  if (pl == nullptr || pl->ins.size() != 1) return DH_EINVAL;
+  return dh_forward_frames_shape((int)pl->ins.size(), pl->ins[0].u8, (int64_t)pl->ins[0].items, pl->n, njobs, OH, OW, m, per_item);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_forward_host(dh_plan* pl, const float* const* inputs_host, int m, float* const* outputs_host) {
+  if (pl == nullptr || inputs_host == nullptr || outputs_host == nullptr || m <= 0 || m > pl->n) return DH_EINVAL;
+  int rc = host_staging(pl);
+  if (rc != DH_OK) return rc;
+  for (size_t i = 0; i < pl->ins.size(); ++i)
+    if (hipMemcpyAsync(pl->in_dev[i], inputs_host[i], pl->ins[i].items * (pl->ins[i].u8 ? 1 : 4) * (size_t)m,
+                       hipMemcpyHostToDevice, pl->stream) != hipSuccess)
+      return DH_ELAUNCH;
+  const size_t used = place_outputs(pl, outputs_host, m);
+  rc = dh_forward(pl, pl->in_dev.data(), m, pl->out_ptr.data(), pl->stream);
+  if (rc != DH_OK) return rc;
+  return fetch_outputs(pl, outputs_host, m, used);
+}
+
+// ---- frames ----------------------------------------------------------------------------------------------------------------
+int dh_frames_create(const dh_crop_src* frames_host, int n, dh_frames** out) {
+  if (frames_host == nullptr || out == nullptr || n < 1) return DH_EINVAL;
+  for (int i = 0; i < n; ++i)
+    if (!dh::crop_src_ok(frames_host[i])) return DH_EINVAL;             // before anything is allocated
+  dh_frames* f = new dh_frames();
+  std::vector<dh_crop_src> table((size_t)n);
+  bool ok = true;
+  for (int i = 0; ok && i < n; ++i) {
+    const dh_crop_src& h = frames_host[i];
+    const size_t row = (size_t)3 * (size_t)h.W;
+    uint8_t* d = nullptr;
+    ok = hipMalloc(&d, row * (size_t)h.H) == hipSuccess;
+    if (ok) f->px.push_back(d);
+    ok = ok && hipMemcpy2D(d, row, h.ptr, (size_t)h.pitch, row, (size_t)h.H, hipMemcpyHostToDevice) == hipSuccess;
+    table[(size_t)i] = dh_crop_src{d, (int64_t)row, h.H, h.W};
+  }
+  ok = ok && hipMalloc(&f->table, (size_t)n * sizeof(dh_crop_src)) == hipSuccess;
+  ok = ok && hipMemcpy(f->table, table.data(), (size_t)n * sizeof(dh_crop_src), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    dh_frames_destroy(f);
+    return DH_ELAUNCH;
+  }
+  *out = f;
+  return DH_OK;
+}
+
+int dh_frames_destroy(dh_frames* f) {
+  if (f == nullptr) return DH_OK;
+  for (uint8_t* d : f->px) hipFree(d);
+  if (f->table) hipFree(f->table);
+  delete f;
+  return DH_OK;
+}
+
+int dh_frames_count(const dh_frames* f) { return f ? (int)f->px.size() : 0; }
+const dh_crop_src* dh_frames_table_dev(const dh_frames* f) { return f ? f->table : nullptr; }
+
+int dh_forward_frames_shape(int num_inputs, int input_is_u8, int64_t input_items, int batch, int njobs, int OH, int OW, int* m,
+                            int* per_item) {
+  if (num_inputs != 1 || input_is_u8 != 1 || input_items < 1 || batch < 1 || njobs < 1 || OH < 1 || OW < 1 ||
+      OH > dh::kCropMaxExtent || OW > dh::kCropMaxExtent)
+    return DH_EINVAL;
+  const int64_t crop = (int64_t)OH * OW * 3;
+  if (input_items % crop != 0) return DH_EINVAL;                         // the input is no stack of [OH, OW, 3] frames
+  const int64_t per = input_items / crop;
+  if (per > 0x7fffffff / batch || njobs % per != 0 || njobs / per > batch) return DH_EINVAL;
+  if (m != nullptr) *m = (int)(njobs / per);
+  if (per_item != nullptr) *per_item = (int)per;
+  return DH_OK;
+}
+
+int dh_forward_frames(dh_plan* pl, const dh_frames* f, const dh_crop_job* jobs_dev, int njobs, int OH, int OW,
+                      float* const* outputs_dev, void* stream) {
+  if (pl == nullptr || f == nullptr || jobs_dev == nullptr || outputs_dev == nullptr) return DH_EINVAL;
+  int m = 0, per_item = 0;
+  int rc = frames_shape(pl, njobs, OH, OW, &m, &per_item);
+  if (rc != DH_OK) return rc;
+  size_t need = 0;                                                     // the program of a FULL batch: one allocation per plan
+  rc = dh_crop_program_max_bytes(pl->n * per_item, (int)f->px.size(), OH, OW, &need);
+  if (rc != DH_OK) return rc;
+  if (pl->crop_prog_bytes < need) {
+    // (hipFree waits for the device: a forward still reading the old program finishes first)
+    if (pl->crop_prog) hipFree(pl->crop_prog);
+    pl->crop_prog = nullptr;
+    pl->crop_prog_bytes = 0;
+    if (hipMalloc(&pl->crop_prog, need) != hipSuccess) return DH_ELAUNCH;
+    pl->crop_prog_bytes = need;
+  }
+  const In& in = pl->ins[0];
+  rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), jobs_dev, njobs, OH, OW, pl->crop_prog, pl->crop_prog_bytes, nullptr,
+                                 stream);
+  if (rc != DH_OK) return rc;
+  rc = dh_crop_resize_u8(pl->crop_prog, njobs, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, stream);
+  if (rc != DH_OK) return rc;
+  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
+  return dh_forward(pl, inputs, m, outputs_dev, stream);
+}
+
+int dh_forward_frames_host(dh_plan* pl, const dh_frames* f, const dh_crop_job* jobs_host, int njobs, int OH, int OW,
+                           float* const* outputs_host) {
+  if (pl == nullptr || f == nullptr || jobs_host == nullptr || outputs_host == nullptr) return DH_EINVAL;
+  int m = 0, per_item = 0;
+  int rc = frames_shape(pl, njobs, OH, OW, &m, &per_item);
+  if (rc != DH_OK) return rc;
+  size_t bytes = 0;                                                    // the host builder's answer to this very table, first
+  rc = dh::crop_program_bytes(jobs_host, njobs, (int)f->px.size(), OH, OW, &bytes);
+  if (rc != DH_OK) return rc;
+  rc = host_staging(pl);
+  if (rc != DH_OK) return rc;
+  const size_t full = (size_t)pl->n * (size_t)per_item;
+  if (pl->crop_jobs_n < full) {
+    if (pl->crop_jobs) hipFree(pl->crop_jobs);
+    pl->crop_jobs = nullptr;
+    pl->crop_jobs_n = 0;
+    if (hipMalloc(&pl->crop_jobs, full * sizeof(dh_crop_job)) != hipSuccess) return DH_ELAUNCH;
+    pl->crop_jobs_n = full;
+  }
+  if (hipMemcpyAsync(pl->crop_jobs, jobs_host, (size_t)njobs * sizeof(dh_crop_job), hipMemcpyHostToDevice, pl->stream) != hipSuccess)
+    return DH_ELAUNCH;
+  const size_t used = place_outputs(pl, outputs_host, m);
+  rc = dh_forward_frames(pl, f, pl->crop_jobs, njobs, OH, OW, pl->out_ptr.data(), pl->stream);
+  if (rc != DH_OK) return rc;
+  return fetch_outputs(pl, outputs_host, m, used);
 }
 
 }  // extern "C"

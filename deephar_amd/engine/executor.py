@@ -821,6 +821,22 @@ class Executor:
                 io['prog_host'][k] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
                 io['prog_dev'][k] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
 
+    def _crop_slots_device(self, io, depth, job_bytes, prog_bytes):
+        """program='device', per slot: pinned host memory for a chunk's JOB table and its device twin (`job_bytes`), and one
+        device buffer of `prog_bytes` the GPU builds the chunk's crop program in.  No pinned program."""
+        torch = _torch()
+        for key in ('jobs_host', 'jobs_dev', 'prog_built'):
+            io.setdefault(key, [])
+        for k in range(depth):
+            if k >= len(io['jobs_host']):
+                for key in ('jobs_host', 'jobs_dev', 'prog_built'):
+                    io[key].append(None)
+            if io['jobs_host'][k] is None or io['jobs_host'][k].numel() < job_bytes:
+                io['jobs_host'][k] = torch.empty(job_bytes, dtype=torch.uint8, pin_memory=True)
+                io['jobs_dev'][k] = torch.empty(job_bytes, dtype=torch.uint8, device=self.device)
+            if io['prog_built'][k] is None or io['prog_built'][k].numel() < prog_bytes:
+                io['prog_built'][k] = torch.empty(prog_bytes, dtype=torch.uint8, device=self.device)
+
     def _host_outputs(self, bp, flat, m):
         """Slice the packed output region (host copy of arena[0 : out_items * n]) into one fresh array per output."""
         torch = _torch()
@@ -857,7 +873,9 @@ class Executor:
            copied in.  host: chunk i+2's crop program (source table, jobs, coefficient tables) is built into pinned memory
            on the pool; copy: the program goes to the device; compute: ONE dh_crop_resize_u8 launch writes the chunk's
            crops straight into the plan's uint8 input, then the same forward and D2H.  Same slots, same events, no host
-           synchronisation between chunks.
+           synchronisation between chunks.  crop.program == 'device': host: chunk i+2's JOB table (24 bytes per crop) goes
+           into pinned memory; copy: the jobs go to the device; compute: dh_crop_program_build_dev builds the program on the
+           GPU from the store's resident source table, then the same crop launch, forward and D2H.
            Returns one np.float32 array per model output, rows in input order (keras Model.predict semantics:
            exp/common/*_tools.py; timing method of exp/pennaction/eval_speed2d.py:70-77)."""
         torch = _torch()
@@ -885,8 +903,14 @@ class Executor:
             depth = max(2, min(nchunks, int(os.environ.get('DEEPHAR_PREDICT_DEPTH', '8')),
                                max(2, (512 << 20) // max(slot_bytes, 1))))
             io = self._io(bp, depth, staged=crop is None)
+            on_gpu = crop is not None and crop.program == 'device'
             if crop is not None:        # (the size query refuses a window beyond the scale cap before anything is enqueued)
-                self._crop_slots(io, depth, max(crop.program_bytes(c0, min(bs, total - c0)) for c0 in range(0, total, bs)))
+                nprog_max = max(crop.program_bytes(c0, min(bs, total - c0)) for c0 in range(0, total, bs))
+                if on_gpu:
+                    self._crop_slots_device(io, depth, 24 * bs * crop.per_item, crop.max_bytes(bs))
+                    srcs_dev = crop.store.srcs_dev
+                else:
+                    self._crop_slots(io, depth, nprog_max)
             io['pending'] = [None] * len(io['pending'])        # a call that died mid-loop must not leak rows into this one
             results = []
             ahead = min(2, depth - 1)                           # chunks staged ahead of the one being enqueued
@@ -906,6 +930,8 @@ class Executor:
                 collect(slot)                                   # chunk ci - depth used this slot (its H2D is long done)
                 m = min(bs, total - start)
                 if crop is not None:                            # the chunk's crop program, built off the main thread
+                    if on_gpu:
+                        return m, None, None, [pool.submit(crop.stage, start, m, io['jobs_host'][slot])]
                     return m, None, None, [pool.submit(crop.build, start, m, io['prog_host'][slot])]
                 on_dev, dev_src, futs = [], [], []
                 for k, (v, arr) in enumerate(zip(self.plan.inputs, arrays)):
@@ -935,9 +961,11 @@ class Executor:
                     slot = ci % depth
                     m, on_dev, dev_src, futs = staged.pop(ci)
                     staged_now = [fu.result() for fu in futs]
-                    nprog = staged_now[0] if crop is not None else 0         # bytes of the chunk's crop program
+                    nprog = staged_now[0] if crop is not None else 0         # bytes of the chunk's crop program / job table
                     with torch.cuda.stream(self.copy_stream):
-                        if crop is not None:
+                        if on_gpu:
+                            io['jobs_dev'][slot][:nprog].copy_(io['jobs_host'][slot][:nprog], non_blocking=True)
+                        elif crop is not None:
                             io['prog_dev'][slot][:nprog].copy_(io['prog_host'][slot][:nprog], non_blocking=True)
                         elif any(on_dev):                         # the caller's device data may still be in flight on ITS stream
                             self.copy_stream.wait_stream(torch.cuda.current_stream())
@@ -950,7 +978,13 @@ class Executor:
                         for k, v in enumerate(self.plan.inputs):
                             dst = bp.u8[id(v.buf)][0] if bp.u8 is not None else bp.tensor(v)
                             if crop is not None:                # no intermediate tensor: the launch fills the plan's input
-                                _lib.check(bp.lib.dh_crop_resize_u8(io['prog_dev'][slot].data_ptr(), m * crop.per_item, crop.OH,
+                                prog = io['prog_built' if on_gpu else 'prog_dev'][slot]
+                                if on_gpu:                      # the program from the jobs, on this stream, in front of the launch
+                                    _lib.check(bp.lib.dh_crop_program_build_dev(
+                                        srcs_dev.data_ptr(), len(crop.store), io['jobs_dev'][slot].data_ptr(), m * crop.per_item,
+                                        crop.OH, crop.OW, prog.data_ptr(), prog.numel(), None, self.stream_ptr),
+                                        'dh_crop_program_build_dev')
+                                _lib.check(bp.lib.dh_crop_resize_u8(prog.data_ptr(), m * crop.per_item, crop.OH,
                                                                     crop.OW, dst.data_ptr(), crop.OH * crop.OW * 3,
                                                                     self.stream_ptr), 'dh_crop_resize_u8')
                                 continue

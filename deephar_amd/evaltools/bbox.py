@@ -34,13 +34,16 @@ def refine_pred(model, frames, afmat, bbox, ds, mode, outidx, num_iter=2, winsiz
     return out
 
 
-def refine_pred_frames(model, frames, bbox0, outidx, num_iter=2, winsize_scale=1.50, momentum=0.8, batch_size=8):
+def refine_pred_frames(model, frames, bbox0, outidx, num_iter=2, winsize_scale=1.50, momentum=0.8, batch_size=8,
+                       program='host'):
     """refine_pred over FULL frames: the same arithmetic, with the re-crop on the GPU (deephar_amd/frontend.py) instead of in
     a dataset.  `frames`: one uint8 [H, W, 3] image per sample (or a frontend.FrameStore), uploaded once for all iterations;
     `bbox0`: the initial float boxes [N, 4] -- what the dataset's `bbox` view shows before any custom box is set.  Every
     iteration crops window crop_box(*bbox_to_objposwin(box)) like the loader does (mpii.py:102-115), unflipped.  Returns
-    the list of per-iteration poses in image coordinates."""
+    the list of per-iteration poses in image coordinates.  `program` is predict_from_frames' keyword, passed on when it is
+    not the default."""
     from .. import frontend
+    extra = {} if program == 'host' else {'program': program}
     if not isinstance(frames, frontend.FrameStore) and hasattr(model, 'executor'):
         frames = frontend.FrameStore(frames, model.executor.device)
     index = np.arange(len(bbox0))
@@ -48,7 +51,7 @@ def refine_pred_frames(model, frames, bbox0, outidx, num_iter=2, winsize_scale=1
     out = []
     for t in range(num_iter):
         windows = np.stack([frontend.crop_box(*bbox_to_objposwin(b)) for b in current])
-        res = frontend.predict_from_frames(model, frames, index, windows, batch_size=batch_size)
+        res = frontend.predict_from_frames(model, frames, index, windows, batch_size=batch_size, **extra)
         pred, A = res[outidx], res[-1]
         pred = transform_pose_sequence(A.copy(), pred, inverse=True)
         out.append(pred)

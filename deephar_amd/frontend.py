@@ -5,6 +5,9 @@ crop_resolution), optional T.horizontal_flip() (deephar/data/mpii.py:114-118, pe
 the box-refinement loop (exp/common/mpii_tools.py:13-52) re-crop the same images again and again.  Here the frames are
 uploaded once (FrameStore) and every chunk's crops are ONE launch (dh_crop_resize_u8) that writes straight into the uint8
 input of the bound plan; the result is bit for bit `model.predict(<the loader's uint8 crops>)`.
+The launch reads a crop program (csrc/crop_index.h).  program='host' (the default) builds it on the host per chunk and copies
+it over; program='device' stages only the chunk's 24-byte jobs and builds the program on the GPU (dh_crop_program_build_dev,
+the same bytes), in front of the crop launch on the compute stream.
 
 Scope: the loaders' test-mode geometry -- angle 0, integer window, bilinear, optional mirror, 3 channels, uint8.  Box and
 matrix bookkeeping stays on the host in float64 (crop_box, crop_afmat), composed like deephar/utils/transform.py does.
@@ -66,6 +69,16 @@ class FrameStore:
         torch.cuda.synchronize(self.device)          # once, at upload: every later launch may read the frames on any stream
         self.srcs = (_lib.CropSrc * len(self.tensors))(*[
             _lib.CropSrc(t.data_ptr(), 3 * t.shape[1], t.shape[0], t.shape[1]) for t in self.tensors])
+        self._srcs_dev = None
+
+    @property
+    def srcs_dev(self):
+        """The source table on the device (what dh_crop_program_build_dev reads), uploaded once, on first use."""
+        if self._srcs_dev is None:
+            import torch
+            self._srcs_dev = torch.from_numpy(np.frombuffer(bytes(self.srcs), np.uint8).copy()).to(self.device)
+            torch.cuda.synchronize(self.device)
+        return self._srcs_dev
 
     def __len__(self):
         return len(self.tensors)
@@ -74,8 +87,10 @@ class FrameStore:
 class CropFeed:
     """What Executor.run_pipelined needs to crop its own input: the per-chunk crop programs over a FrameStore."""
 
-    def __init__(self, store, index, boxes, hflip, out_hw):
-        self.store, self.lib = store, _lib.load()
+    def __init__(self, store, index, boxes, hflip, out_hw, program='host'):
+        if program not in ('host', 'device'):
+            raise ValueError("program must be 'host' or 'device', got %r" % (program,))
+        self.store, self.lib, self.program = store, _lib.load(), program
         self.index = np.asarray(index, np.int64)
         self.boxes = np.asarray(boxes, np.int64)
         self.hflip = np.asarray(hflip).astype(bool)
@@ -115,8 +130,29 @@ class CropFeed:
                                                        out.data_ptr(), nbytes), 'dh_crop_program_build_host')
         return nbytes
 
+    # ---- program='device': a chunk's staging is its job table, the program is built by the GPU
+    def max_bytes(self, m):
+        """What the device program of a chunk of m items can take (dh_crop_program_max_bytes)."""
+        nbytes = C.c_size_t(0)
+        rc = self.lib.dh_crop_program_max_bytes(m * self.per_item, len(self.store), self.OH, self.OW, C.byref(nbytes))
+        if rc == -2:
+            raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % (m * self.per_item))
+        _lib.check(rc, 'dh_crop_program_max_bytes')
+        return nbytes.value
 
-def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32):
+    def stage(self, start, m, out):
+        """The job table of items [start, start + m) -- 24 bytes per job, nothing else -- into the uint8 tensor `out`; returns
+        its bytes."""
+        import torch
+        part = self.jobs[start * self.per_item:(start + m) * self.per_item]
+        nbytes = part.size * 4
+        if out.numel() < nbytes:
+            raise ValueError('job staging too small')
+        out[:nbytes].copy_(torch.from_numpy(part.reshape(-1).view(np.uint8)))
+        return nbytes
+
+
+def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32, program='host'):
     """model.predict on crops of full frames, cropped on the GPU.
 
     frames : a FrameStore, or a sequence of uint8 [H, W, 3] arrays (uploaded once, here)
@@ -125,7 +161,11 @@ def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32):
              clip-level box is broadcast over the clip's frames)
     hflip  : None, one flag, or one per item ([N]) or per frame ([N, T])
     Returns the outputs of model.predict as a list, followed by the float64 affine maps [N(, T), 3, 3] (crop_afmat).
+    program: 'host' -- every chunk's crop program is built on the host and copied to the device; 'device' -- only the chunk's
+             jobs are staged and the program is built on the GPU in front of the crop launch.  The same bits either way.
     Bit for bit model.predict(<uint8 crops of the loader>, batch_size)."""
+    if program not in ('host', 'device'):
+        raise ValueError("program must be 'host' or 'device', got %r" % (program,))
     if len(model.inputs) != 1:
         raise ValueError('predict_from_frames needs a model with a single image input, %s has %d inputs' %
                          (model.name, len(model.inputs)))
@@ -151,7 +191,7 @@ def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32):
         return [np.zeros((0,) + tuple(t.shape), np.float32) for t in model.outputs] + [afmat]
     ex = model.executor
     store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
-    feed = CropFeed(store, index, boxes, flips, (OH, OW))
+    feed = CropFeed(store, index, boxes, flips, (OH, OW), program)
     bs = int(min(batch_size or feed.total, feed.total))
     outs = ex.run_pipelined(None, bs, u8_norm=model.channel_power, crop=feed)
     return list(outs) + [afmat]

@@ -143,14 +143,20 @@ def normalize_u8(x, lut):
     return y
 
 
-def crop_resize(sources, jobs, out_hw, out=None, item_pitch=None):
+def crop_resize(sources, jobs, out_hw, out=None, item_pitch=None, program='host'):
     """Crop-and-resize front end (dh_crop_resize_u8): every job in one launch on torch's current stream.
     sources: uint8 CUDA tensors [H, W, 3], rows contiguous (a row pitch above 3 W is fine: a column slice of a wider
     image); jobs: (source index, (x0, y0, x1, y1), hflip); out_hw = (OH, OW).  Returns uint8 [len(jobs), OH, OW, 3], bit for
     bit PIL's Image.crop(box).resize((OW, OH), BILINEAR) [mirrored].  `out`: a flat uint8 CUDA tensor to write into, item j
-    at byte j * item_pitch (the op then returns `out`).  ValueError for a window more than 16 times its output."""
+    at byte j * item_pitch (the op then returns `out`).  ValueError for a window more than 16 times its output.
+    program='device': the crop program is built on the GPU (dh_crop_program_build_dev) from the uploaded source and job tables
+    instead of on the host -- the same bytes, the same output; the per-job status is read back before the crop launch, which
+    SYNCHRONISES the current stream (fine for an op; the pipelined front end does not read it), and any refused job raises the
+    ValueError the host path raises, before anything is written."""
     torch = _t()
     lib = _lib.load()
+    if program not in ('host', 'device'):
+        raise ValueError("program must be 'host' or 'device', got %r" % (program,))
     OH, OW = int(out_hw[0]), int(out_hw[1])
     srcs = (_lib.CropSrc * len(sources))()
     for i, s in enumerate(sources):
@@ -160,17 +166,32 @@ def crop_resize(sources, jobs, out_hw, out=None, item_pitch=None):
     cj = (_lib.CropJob * len(jobs))(*[_lib.CropJob(int(s), int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(bool(f)))
                                       for s, b, f in jobs])
     nbytes = C.c_size_t(0)
-    rc = lib.dh_crop_program_bytes(cj, len(jobs), len(sources), OH, OW, C.byref(nbytes))
-    if rc == 0:
-        prog = torch.empty(nbytes.value, dtype=torch.uint8, pin_memory=True)
-        rc = lib.dh_crop_program_build_host(srcs, len(sources), cj, len(jobs), OH, OW, prog.data_ptr(), nbytes.value)
+    device = sources[0].device
+    if program == 'device':
+        what = 'dh_crop_program_build_dev'
+        rc = lib.dh_crop_program_max_bytes(len(jobs), len(sources), OH, OW, C.byref(nbytes))
+        if rc == 0:
+            tables = [torch.from_numpy(np.frombuffer(bytes(t), np.uint8).copy()).to(device) for t in (srcs, cj)]
+            prog_dev = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+            status = torch.empty(len(jobs), dtype=torch.int32, device=device)
+            rc = lib.dh_crop_program_build_dev(tables[0].data_ptr(), len(sources), tables[1].data_ptr(), len(jobs), OH, OW,
+                                               prog_dev.data_ptr(), nbytes.value, status.data_ptr(), _stream())
+        if rc == 0:
+            codes = status.cpu().numpy()                       # the synchronisation the docstring speaks of
+            rc = -1 if np.any(codes == -1) else (-2 if np.any(codes == -2) else int(codes.min()))
+    else:
+        what = 'dh_crop_program_build_host'
+        rc = lib.dh_crop_program_bytes(cj, len(jobs), len(sources), OH, OW, C.byref(nbytes))
+        if rc == 0:
+            prog = torch.empty(nbytes.value, dtype=torch.uint8, pin_memory=True)
+            rc = lib.dh_crop_program_build_host(srcs, len(sources), cj, len(jobs), OH, OW, prog.data_ptr(), nbytes.value)
     if rc == -2:
         raise ValueError('crop_resize: a window is more than 16 times its output on one axis, or the output is too wide')
     if rc == -1:
         raise ValueError('crop_resize: bad argument (empty box, source index, row pitch below 3 W)')
-    _lib.check(rc, 'dh_crop_program_build_host')
-    device = sources[0].device
-    prog_dev = prog.to(device, non_blocking=True)
+    _lib.check(rc, what)
+    if program == 'host':
+        prog_dev = prog.to(device, non_blocking=True)
     if out is None:
         item_pitch = OH * OW * 3
         y = torch.empty((len(jobs), OH, OW, 3), dtype=torch.uint8, device=device)

@@ -641,7 +641,7 @@ int dh_clip_input_is_u8(const dh_clip* clip);
  * call it), i.e. PIL's Image.crop(box).resize(size, BILINEAR) [.transpose(FLIP_LEFT_RIGHT)] on 8-bit RGB -- bit for bit:
  * PIL's 8-bit resize is integer arithmetic on fixed-point coefficients, restated in csrc/crop_index.h.
  *   crop   : C[y, x] = S[y0 + y, x0 + x] inside the image, 0 outside; cw = x1 - x0, ch = y1 - y0.
- *   axis   : (in, out) = (cw, OW) or (ch, OH), all in double ON THE HOST: scale = in / out, fs = max(scale, 1), support = fs,
+ *   axis   : (in, out) = (cw, OW) or (ch, OH), all in double, never fused: scale = in / out, fs = max(scale, 1), support = fs,
  *            ss = 1 / fs; output i: center = (i + 0.5) * scale, xmin = max(0, (int)(center - support + 0.5)),
  *            xmax = min(in, (int)(center + support + 0.5)), w_j = max(0, 1 - |(j + xmin - center + 0.5) * ss|) normalised by
  *            their sum, k_j = (int)(0.5 + w_j * 2^22).
@@ -674,6 +674,62 @@ int dh_crop_resize_host(const void* program_host, size_t bytes, int njobs, int O
  * first[out], count[out], k[out * taps] with taps >= dh_crop_axis_taps(in, out) */
 int dh_crop_axis_taps(int in, int out);
 int dh_crop_axis_coeffs_host(int in, int out, int taps, int32_t* first, int32_t* count, int32_t* k);
+/* The crop program built ON THE DEVICE from a job table in device memory, for callers whose boxes never visit the host.
+ *   max_bytes: what a program of njobs jobs over nsrc sources can take at most (both axis tables of every job at the 33 taps
+ *            of the scale cap): what the caller allocates before the boxes are known.  >= dh_crop_program_bytes of every
+ *            table that query accepts.  DH_EINVAL: njobs / nsrc < 1, extents, NULL; DH_EUNSUPPORTED: above 2^31 - 1 bytes.
+ *   build_dev: srcs_dev (8-byte aligned), jobs_dev, program_dev (8-byte aligned, `capacity` bytes) and status_dev (njobs
+ *            int32, may be NULL) are DEVICE memory; two small launches on `stream` (layout: one work-group validates the
+ *            jobs, scans their table sizes into offsets, writes header, source table and job records; tables: one work-group
+ *            per job and axis, one lane per output index), nothing synchronises, no atomics.  The doubles are the host
+ *            builder's, operation for operation, with contraction into fused multiply-adds switched off on both sides
+ *            (csrc/crop_index.h): for a table in which every job is good, the first header.bytes bytes of program_dev are,
+ *            byte for byte, what dh_crop_program_build_host writes for the same sources and jobs, and header.bytes is what
+ *            dh_crop_program_bytes answers.  Nothing is written at or beyond program_dev + header.bytes.
+ *            A job that is no good -- empty box, source index out of range, a source descriptor dh_crop_program_build_host
+ *            would refuse (status DH_EINVAL), or a window beyond the scale cap (DH_EUNSUPPORTED) -- gets a record without
+ *            tables that dh_crop_resize_u8 skips: its output item is left untouched, the other jobs run; status[j] of a good
+ *            job is DH_OK.  Reading the status back is the caller's business (and a synchronisation).
+ *            Refused on the host, before anything is enqueued: DH_EINVAL for NULL / misaligned pointers, extents and
+ *            capacity < max_bytes; DH_EUNSUPPORTED when 33 rows of the output width do not fit LDS (OW > 661: narrower than
+ *            what the host builder takes for windows of small scale, because here the scale is not known on the host). */
+int dh_crop_program_max_bytes(int njobs, int nsrc, int OH, int OW, size_t* bytes);
+int dh_crop_program_build_dev(const dh_crop_src* srcs_dev, int nsrc, const dh_crop_job* jobs_dev, int njobs, int OH, int OW,
+                              void* program_dev, size_t capacity, int32_t* status_dev /* may be NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Frames and boxes through a plan, for hosts without Python: what deephar_amd/frontend.py's predict_from_frames does.
+ *   frames : dh_frames_create uploads n full uint8 [H, W, 3] frames ONCE (frames_host[i].ptr is HOST memory, pitch >= 3 * W
+ *            bytes between rows; sizes may differ) and keeps the device source table dh_frames_table_dev returns (n
+ *            descriptors with device `ptr`, dense rows) -- what dh_crop_program_build_dev takes as srcs_dev.  Create and
+ *            destroy synchronise; DH_EINVAL: NULL, n < 1, a descriptor with NULL ptr / H or W < 1 / pitch < 3 * W.
+ *   forward_frames: `plan` has exactly one input and it is uint8 (Model.export_plan(path, batch, uint8=True)).  The blob does
+ *            not carry the input's height and width, so the caller states OH and OW: dh_plan_input_items(plan, 0) must be
+ *            T * OH * OW * 3 for a whole T (1: an image model; T frames per clip of a clip model) and njobs = m * T for an
+ *            m in [1, dh_plan_batch]; job j is frame j % T of item j / T.  Anything else is DH_EINVAL
+ *            (dh_forward_frames_shape is that test on its own, GPU-free; it answers m and T).
+ *            jobs_dev is DEVICE memory (src indexes the frames of `f`).  Enqueued on `stream`, in this order:
+ *            dh_crop_program_build_dev into the plan's program buffer (allocated on first use for a full batch, freed by
+ *            dh_plan_destroy), dh_crop_resize_u8 straight into the plan's uint8 input, the forward of dh_forward with its
+ *            input copy skipped.  Nothing synchronises.  A multi-stream plan runs the two launches on `stream` in front of
+ *            its fork.  A job the builder refuses leaves its frame of the input as the previous call left it: a caller
+ *            that cannot vouch for its boxes calls dh_crop_program_build_dev itself and reads the status.
+ *            outputs_dev as in dh_forward.  Results are bit-identical to predict_from_frames of the exporting process.
+ *   forward_frames_host: jobs and outputs are HOST memory; the table is validated on the host first (dh_crop_program_bytes:
+ *            a bad table is refused with that code before anything is enqueued), staged, run on the plan's internal stream;
+ *            returns when the outputs are on the host, like dh_forward_host.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_frames dh_frames;
+int dh_frames_create(const dh_crop_src* frames_host, int n, dh_frames** out);
+int dh_frames_destroy(dh_frames* f);
+int dh_frames_count(const dh_frames* f);
+const dh_crop_src* dh_frames_table_dev(const dh_frames* f);
+int dh_forward_frames_shape(int num_inputs, int input_is_u8, int64_t input_items, int batch, int njobs, int OH, int OW, int* m,
+                            int* frames_per_item);
+int dh_forward_frames(dh_plan* plan, const dh_frames* f, const dh_crop_job* jobs_dev, int njobs, int OH, int OW,
+                      float* const* outputs_dev, void* stream);
+int dh_forward_frames_host(dh_plan* plan, const dh_frames* f, const dh_crop_job* jobs_host, int njobs, int OH, int OW,
+                           float* const* outputs_host);
 
 /* ---------------------------------------------------------------------------------------------------
  * Stream-ordered runtime helpers (no torch types): graphs for launch-bound replay, events for timing.

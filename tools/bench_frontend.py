@@ -1,13 +1,16 @@
 """Measure the crop-and-resize front end on one GPU; writes profiles/frontend_crop.json.
 
-    python tools/bench_frontend.py [--out profiles/frontend_crop.json] [--frames 2048] [--reps 3]
+    python tools/bench_frontend.py [--out profiles/frontend_crop.json] [--frames 2048] [--reps 5]
 
 (a) the crop launch alone: 64 jobs out of 720 x 1280 frames, seeded windows of 250 - 900 px -> 256 x 256, device events around
     `iters` launches after a warm-up; algorithmic bytes = clipped window area read + output written; GB/s and the share of the
     8.0 TB/s HBM roof.
-(b) the MPII workload of bench.py (ReceptionNet, 8 blocks, batch 64): predict_from_frames (full frames resident on the device,
-    crops on the GPU) alternating with Model.predict on pre-cropped uint8 frames, in one process, `reps` repetitions each,
-    wall clock per call; the difference is reported beside the spread of the baseline leg's repetitions.
+    The same jobs through dh_crop_program_build_dev (the program built on the GPU: a layout launch and a table launch), the
+    pair timed the same way: `build_dev_ms_per_pair`.
+(b) the MPII workload of bench.py (ReceptionNet, 8 blocks, batch 64): Model.predict on pre-cropped uint8 frames,
+    predict_from_frames with program='host' (a chunk's crop program built on the host and copied over) and with
+    program='device' (only the chunk's jobs staged, the program built on the GPU), alternating in one process, `reps`
+    repetitions each, wall clock per call; the differences are reported beside the spread of the baseline leg's repetitions.
 (c) where PIL imports: Image.crop(box).resize((256, 256), BILINEAR) on this machine's CPU, one core, per frame -- the CPU
     baseline the front end replaces; the machine's core count is recorded with it.
 """
@@ -69,12 +72,36 @@ def bench_launch(torch, iters=50, warmup=5):
     ev[1].record()
     torch.cuda.synchronize()
     ms = ev[0].elapsed_time(ev[1]) / iters
+    # the same program built on the device: both tables uploaded once, the launch pair timed like the crop launch
+    cap = C.c_size_t(0)
+    _lib.check(lib.dh_crop_program_max_bytes(n, len(frames), 256, 256, C.byref(cap)))
+    srcs_dev = torch.from_numpy(np.frombuffer(bytes(srcs), np.uint8).copy()).cuda()
+    jobs_dev = torch.from_numpy(np.frombuffer(bytes(cj), np.uint8).copy()).cuda()
+    built = torch.zeros(cap.value, dtype=torch.uint8, device='cuda')
+    status = torch.empty(n, dtype=torch.int32, device='cuda')
+
+    def build_pair():
+        _lib.check(lib.dh_crop_program_build_dev(srcs_dev.data_ptr(), len(frames), jobs_dev.data_ptr(), n, 256, 256, built.data_ptr(),
+                                                 cap.value, status.data_ptr(), st))
+    for _ in range(warmup):
+        build_pair()
+    torch.cuda.synchronize()
+    same = bool((built[:nbytes.value] == prog).all()) and not bool(status.any())
+    ev2 = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    pair_iters = 40 * iters                                  # (a pair is microseconds: enough of them for a window of milliseconds)
+    ev2[0].record()
+    for _ in range(pair_iters):
+        build_pair()
+    ev2[1].record()
+    torch.cuda.synchronize()
+    pair_ms = ev2[0].elapsed_time(ev2[1]) / pair_iters       # back-to-back pairs on one stream: a rate, not one pair's latency
     read = sum(clipped_area(b, H, W) for b in boxes) * 3
     written = n * 256 * 256 * 3
     gbs = (read + written) / (ms * 1e-3) / 1e9
     return dict(jobs=n, source='720x1280', output='256x256', windows_px='250-900, seeded', iters=iters, ms_per_launch=ms,
                 us_per_frame=ms * 1e3 / n, bytes_read=int(read), bytes_written=int(written), gb_per_s=gbs,
-                share_of_hbm_roof=gbs / HBM_ROOF_GBS, program_bytes=int(nbytes.value), program_build_ms_host=build_ms)
+                share_of_hbm_roof=gbs / HBM_ROOF_GBS, program_bytes=int(nbytes.value), program_build_ms_host=build_ms,
+                build_dev_ms_per_pair=pair_ms, build_dev_pairs_timed=pair_iters, build_dev_capacity_bytes=int(cap.value), build_dev_equals_host_program=same)
 
 
 def bench_predict(torch, total, reps, batch=64, blocks=8):
@@ -89,7 +116,9 @@ def bench_predict(torch, total, reps, batch=64, blocks=8):
     store = frontend.FrameStore(full)
     crops = rng.integers(0, 256, (total, 256, 256, 3), dtype=np.uint8)            # pre-cropped frames: the baseline's input
     legs = {'predict_precropped_u8': lambda: model.predict(crops, batch_size=batch),
-            'predict_from_frames': lambda: frontend.predict_from_frames(model, store, index, boxes, batch_size=batch)}
+            'predict_from_frames': lambda: frontend.predict_from_frames(model, store, index, boxes, batch_size=batch),
+            'predict_from_frames_program_device': lambda: frontend.predict_from_frames(model, store, index, boxes, batch_size=batch,
+                                                                                       program='device')}
     for fn in legs.values():                                                     # bind, autotune, capture, staging
         fn()
     times = {k: [] for k in legs}
@@ -106,6 +135,14 @@ def bench_predict(torch, total, reps, batch=64, blocks=8):
     res['difference_ms_per_batch'] = (float(np.median(front)) - float(np.median(base))) / (total / batch) * 1e3
     res['baseline_spread_ms_per_batch'] = (max(base) - min(base)) / (total / batch) * 1e3
     res['front_end_relative_to_baseline'] = float(np.median(base)) / float(np.median(front))
+    dev = times['predict_from_frames_program_device']
+    res['program_device'] = {
+        'difference_to_baseline_ms_per_batch': (float(np.median(dev)) - float(np.median(base))) / (total / batch) * 1e3,
+        'difference_to_program_host_ms_per_batch': (float(np.median(dev)) - float(np.median(front))) / (total / batch) * 1e3,
+        'relative_to_baseline': float(np.median(base)) / float(np.median(dev)),
+        'relative_to_program_host': float(np.median(front)) / float(np.median(dev)),
+        'ahead_of_program_host_by_more_than_the_baseline_spread':
+            bool((float(np.median(front)) - float(np.median(dev))) > (max(base) - min(base)))}
     return res
 
 
@@ -131,7 +168,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'frontend_crop.json'))
     ap.add_argument('--frames', type=int, default=2048)
-    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=5)
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), 'bench_frontend needs a HIP device'

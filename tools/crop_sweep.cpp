@@ -4,11 +4,15 @@
 //       tools/crop_sweep.cpp -o /tmp/crop_sweep && /tmp/crop_sweep
 //
 // 1. dh::crop_axis_coeffs over a grid of (in, out): tables in heap blocks of exactly their length; first / count inside the
-//    axis, count <= taps, every k >= 0, the k of an output sum to 2^22 within one unit per tap.
+//    axis, count <= taps, every k >= 0, the k of an output sum to 2^22 within one unit per tap.  dh::crop_axis_output, the
+//    per-output function the device builder runs one lane per index of, called for single indices in DESCENDING order into
+//    blocks of their own: the same table, and nothing outside row i is touched.
 // 2. crop programs over a grid of image sizes, output sizes and windows (inside, overhanging every edge, fully outside, one
 //    pixel wide, scale exactly 16), several jobs and sources per program, row pitches above 3 W: program, sources and
 //    destination each in a heap block of exactly its length, guard bytes around every destination item; dh::crop_resize_host
 //    against the two passes written out long-hand with a materialised crop and a materialised horizontal intermediate.
+//    dh::crop_program_max_bytes covers every one of them, is reached exactly by a table of jobs at the scale cap, and the 4
+//    bytes behind a table of odd length are written (0) whatever the buffer held.
 // 3. refusals: scale above 16 (DH_EUNSUPPORTED, nothing written), empty boxes, bad source index, short pitch, short program
 //    buffer, and programs with one field broken (DH_EINVAL each, destination untouched).
 // Not a pytest test: nothing here is loaded into Python.
@@ -57,6 +61,17 @@ static void sweep_axes() {
         }
         if (sum < (1 << 22) - a.taps || sum > (1 << 22) + a.taps) die("coefficients do not sum to one", in, out);
       }
+      // one output at a time, last index first, into tables filled with a sentinel
+      const int32_t mark = -77;
+      std::vector<int32_t> first(out, mark), count(out, mark), k((size_t)out * a.taps, mark);
+      const CropAxis ax = crop_axis_setup(in, out);
+      for (int i = out - 1; i >= 0; --i) {
+        crop_axis_output(ax, in, a.taps, i, first.data(), count.data(), k.data());
+        for (int r = 0; r < i; ++r)
+          if (first[r] != mark || count[r] != mark || k[(size_t)r * a.taps] != mark || k[(size_t)(r + 1) * a.taps - 1] != mark)
+            die("crop_axis_output wrote outside its row", in, out);
+      }
+      if (first != a.first || count != a.count || k != a.k) die("per-output tables differ from the axis loop", in, out);
       ++n_axes;
     }
 }
@@ -137,7 +152,14 @@ static void sweep_programs() {
     if (crop_program_bytes(jobs.data(), njobs, nsrc, OH, OW, &bytes) != DH_OK) die("size query refused a good table", round);
     std::vector<uint64_t> store(bytes / 8);                                    // exactly the program, 8-byte aligned
     if (bytes % 8) die("program size is no multiple of 8", (long long)bytes);
+    if (crop_program_max_bytes(njobs, nsrc, OH, OW) < bytes) die("capacity below a program", round);
+    std::fill(store.begin(), store.end(), 0xCDCDCDCDCDCDCDCDull);             // the padding behind odd tables must be written
     if (crop_program_build(srcs.data(), nsrc, jobs.data(), njobs, OH, OW, store.data(), bytes) != DH_OK) die("builder refused", round);
+    for (int j = 0; j < njobs; ++j) {
+      const CropJobView v = crop_job_view(store.data(), j, OH, OW);
+      if (crop_axis_table_pad(OW, v.rec.xtaps) && v.xk[(size_t)OW * v.rec.xtaps] != 0) die("x table padding", round, j);
+      if (crop_axis_table_pad(OH, v.rec.ytaps) && v.yk[(size_t)OH * v.rec.ytaps] != 0) die("y table padding", round, j);
+    }
     const int64_t item = (int64_t)OH * OW * 3 + guard;
     std::vector<uint8_t> y((size_t)(item * njobs), 0xCD);
     if (crop_resize_host(store.data(), bytes, njobs, OH, OW, y.data(), item) != DH_OK) die("host twin refused", round);
@@ -170,6 +192,24 @@ static void sweep_programs() {
     if (crop_resize_host(store.data(), bytes, njobs, OH, OW, y.data(), item - guard - 1) != DH_EINVAL) die("short item pitch accepted", round);
     n_refused += 2;
   }
+}
+
+static void sweep_capacity() {
+  for (int OH : {1, 4, 7, 256})
+    for (int OW : {1, 5, 8, 256})
+      for (int njobs : {1, 3, 64}) {
+        std::vector<dh_crop_job> jobs((size_t)njobs, dh_crop_job{0, -3, 2, -3 + 16 * OW, 2 + 16 * OH, 0});   // every job at the cap
+        size_t bytes = 0;
+        if (crop_program_bytes(jobs.data(), njobs, 2, OH, OW, &bytes) != DH_OK) die("cap table refused", OH, OW);
+        if (crop_program_max_bytes(njobs, 2, OH, OW) != bytes) die("capacity is not the program at the cap", OH, OW);
+        jobs[0].x1 = jobs[0].x0 + 1;                                                                          // one job up-scaled: 3 taps
+        if (crop_program_bytes(jobs.data(), njobs, 2, OH, OW, &bytes) != DH_OK || crop_program_max_bytes(njobs, 2, OH, OW) <= bytes)
+          die("capacity does not exceed a smaller program", OH, OW);
+      }
+  if (crop_program_max_bytes(0, 1, 8, 8) != 0 || crop_program_max_bytes(1, 0, 8, 8) != 0 || crop_program_max_bytes(1, 1, 0, 8) != 0 ||
+      crop_program_max_bytes(1, 1, 8, kCropMaxExtent + 1) != 0)
+    die("capacity of a bad argument");
+  n_refused += 4;
 }
 
 static void sweep_refusals() {
@@ -217,6 +257,7 @@ static void sweep_refusals() {
 int main() {
   sweep_axes();
   sweep_programs();
+  sweep_capacity();
   sweep_refusals();
   std::printf("crop_sweep: %lld axes, %lld jobs equal to the long-hand passes, %lld refusals -- clean\n", n_axes, n_jobs, n_refused);
   return 0;
