@@ -14,6 +14,7 @@
 #include "dh_kernels.h"
 #include "plan_sched.h"
 #include "crop_index.h"
+#include "refine_index.h"
 
 namespace {
 
@@ -57,6 +58,10 @@ struct dh_plan {
   size_t crop_prog_bytes = 0;
   dh_crop_job* crop_jobs = nullptr;
   size_t crop_jobs_n = 0;
+  // dh_refine_frames_host (allocated on first use, grown when a call needs more): the box table, the job tables and the
+  // builder's status of every iteration, the frame indices and the raw poses of every iteration, in ONE allocation
+  char* refine_buf = nullptr;
+  size_t refine_bytes = 0;
 };
 
 // full frames resident on the device: dense rows (pitch 3 * W), one allocation per frame, and the source table of the launch
@@ -405,6 +410,7 @@ int dh_plan_destroy(dh_plan* pl) {
   if (pl->bytes) hipFree(pl->bytes);
   if (pl->crop_prog) hipFree(pl->crop_prog);
   if (pl->crop_jobs) hipFree(pl->crop_jobs);
+  if (pl->refine_buf) hipFree(pl->refine_buf);
   delete pl;
   return DH_OK;
 }
@@ -421,6 +427,7 @@ int dh_plan_input_is_u8(const dh_plan* pl, int i) {
 int64_t dh_plan_output_items(const dh_plan* pl, int i) {
   return (pl && i >= 0 && i < (int)pl->outs.size()) ? (int64_t)(pl->outs[i].npix * pl->outs[i].C) : -1;
 }
+int dh_plan_output_channels(const dh_plan* pl, int i) { return (pl && i >= 0 && i < (int)pl->outs.size()) ? pl->outs[i].C : -1; }
 
 float* dh_plan_input_ptr(const dh_plan* pl, int i) {
   return (pl && i >= 0 && i < (int)pl->ins.size() && pl->ins[i].u8 == 0) ? reinterpret_cast<float*>(pl->ins[i].dst) : nullptr;
@@ -550,6 +557,22 @@ int fetch_outputs(dh_plan* pl, float* const* outputs_host, int m, size_t used) {
   return DH_OK;
 }
 
+// the plan's device crop program, large enough for a FULL batch over the frames of `f`: one allocation per plan
+int crop_program_room(dh_plan* pl, const dh_frames* f, int per_item, int OH, int OW) {
+  size_t need = 0;
+  const int rc = dh_crop_program_max_bytes(pl->n * per_item, (int)f->px.size(), OH, OW, &need);
+  if (rc != DH_OK) return rc;
+  if (pl->crop_prog_bytes < need) {
+    // (hipFree waits for the device: a forward still reading the old program finishes first)
+    if (pl->crop_prog) hipFree(pl->crop_prog);
+    pl->crop_prog = nullptr;
+    pl->crop_prog_bytes = 0;
+    if (hipMalloc(&pl->crop_prog, need) != hipSuccess) return DH_ELAUNCH;
+    pl->crop_prog_bytes = need;
+  }
+  return DH_OK;
+}
+
 // dh_forward_frames_shape of this plan: the items `njobs` crops of OH x OW x 3 bytes fill and the frames per item, or DH_EINVAL
 int frames_shape(const dh_plan* pl, int njobs, int OH, int OW, int* m, int* per_item) {
   if (pl == nullptr || pl->ins.size() != 1) return DH_EINVAL;
@@ -632,17 +655,8 @@ int dh_forward_frames(dh_plan* pl, const dh_frames* f, const dh_crop_job* jobs_d
   int m = 0, per_item = 0;
   int rc = frames_shape(pl, njobs, OH, OW, &m, &per_item);
   if (rc != DH_OK) return rc;
-  size_t need = 0;                                                     // the program of a FULL batch: one allocation per plan
-  rc = dh_crop_program_max_bytes(pl->n * per_item, (int)f->px.size(), OH, OW, &need);
+  rc = crop_program_room(pl, f, per_item, OH, OW);
   if (rc != DH_OK) return rc;
-  if (pl->crop_prog_bytes < need) {
-    // (hipFree waits for the device: a forward still reading the old program finishes first)
-    if (pl->crop_prog) hipFree(pl->crop_prog);
-    pl->crop_prog = nullptr;
-    pl->crop_prog_bytes = 0;
-    if (hipMalloc(&pl->crop_prog, need) != hipSuccess) return DH_ELAUNCH;
-    pl->crop_prog_bytes = need;
-  }
   const In& in = pl->ins[0];
   rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), jobs_dev, njobs, OH, OW, pl->crop_prog, pl->crop_prog_bytes, nullptr,
                                  stream);
@@ -678,6 +692,81 @@ int dh_forward_frames_host(dh_plan* pl, const dh_frames* f, const dh_crop_job* j
   rc = dh_forward_frames(pl, f, pl->crop_jobs, njobs, OH, OW, pl->out_ptr.data(), pl->stream);
   if (rc != DH_OK) return rc;
   return fetch_outputs(pl, outputs_host, m, used);
+}
+
+// ---- the box-refinement loop of one batch, boxes resident on the device ----------------------------------------------------------
+int dh_refine_frames_host(dh_plan* pl, const dh_frames* f, const int32_t* src, const double* boxes0, int n, int OH, int OW, int outidx,
+                          int num_iter, double winsize_scale, double momentum, float* poses_out, dh_crop_job* jobs_out,
+                          int32_t* status_out) {
+  if (pl == nullptr || f == nullptr || src == nullptr || boxes0 == nullptr || poses_out == nullptr || jobs_out == nullptr ||
+      status_out == nullptr || pl->ins.size() != 1 || outidx < 0 || outidx >= (int)pl->outs.size())
+    return DH_EINVAL;
+  const Out& o = pl->outs[(size_t)outidx];
+  int J = 0;
+  int rc = dh::refine_frames_shape((int)pl->ins.size(), pl->ins[0].u8, (int64_t)pl->ins[0].items, pl->n, n, OH, OW, (int)pl->outs.size(),
+                                   outidx, (int64_t)(o.npix * (size_t)o.C), o.C, num_iter, &J);
+  if (rc != DH_OK) return rc;
+  if ((int64_t)num_iter * pl->n > 0x7fffffff / 64) return DH_EINVAL;
+  rc = host_staging(pl);
+  if (rc != DH_OK) return rc;
+  rc = crop_program_room(pl, f, 1, OH, OW);
+  if (rc != DH_OK) return rc;
+  // one allocation for a full batch: boxes | jobs of every iteration | status of every iteration | src | poses of every iteration
+  const size_t N = (size_t)pl->n, T = (size_t)num_iter;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t pose_floats = stage_floats(o, pl->n);                   // per iteration, a 16-byte multiple
+  const size_t off_jobs = up16(32 * N), off_status = off_jobs + up16(sizeof(dh_crop_job) * N * T);
+  const size_t off_src = off_status + up16(4 * N * T), off_poses = off_src + up16(4 * N);
+  const size_t need = off_poses + pose_floats * 4 * T;
+  if (pl->refine_bytes < need) {
+    if (pl->refine_buf) hipFree(pl->refine_buf);
+    pl->refine_buf = nullptr;
+    pl->refine_bytes = 0;
+    if (hipMalloc(&pl->refine_buf, need) != hipSuccess) return DH_ELAUNCH;
+    pl->refine_bytes = need;
+  }
+  double* boxes = reinterpret_cast<double*>(pl->refine_buf);
+  dh_crop_job* jobs = reinterpret_cast<dh_crop_job*>(pl->refine_buf + off_jobs);
+  int32_t* status = reinterpret_cast<int32_t*>(pl->refine_buf + off_status);
+  int32_t* src_dev = reinterpret_cast<int32_t*>(pl->refine_buf + off_src);
+  float* poses = reinterpret_cast<float*>(pl->refine_buf + off_poses);
+  hipStream_t s = pl->stream;
+  if (hipMemcpyAsync(boxes, boxes0, 32 * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(src_dev, src, 4 * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess)
+    return DH_ELAUNCH;
+  rc = dh_jobs_from_boxes_f64(boxes, src_dev, n, jobs, s);
+  if (rc != DH_OK) return rc;
+  const In& in = pl->ins[0];
+  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
+  const float* view = reinterpret_cast<const float*>(pl->arena + o.off);
+  for (int t = 0; t < num_iter; ++t) {
+    dh_crop_job* jt = jobs + (size_t)t * (size_t)n;
+    rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), jt, n, OH, OW, pl->crop_prog, pl->crop_prog_bytes,
+                                   status + (size_t)t * (size_t)n, s);
+    if (rc == DH_OK) rc = dh_crop_resize_u8(pl->crop_prog, n, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, s);
+    if (rc != DH_OK) break;
+    pl->out_ptr.assign(pl->outs.size(), nullptr);                      // only the pose output is packed
+    pl->out_ptr[(size_t)outidx] = poses + (size_t)t * pose_floats;
+    rc = dh_forward(pl, inputs, n, pl->out_ptr.data(), s);
+    if (rc != DH_OK) break;
+    // the next window from the poses where the forward left them: same stream, behind the plan's join -- no event
+    if (t + 1 < num_iter)
+      rc = dh_refine_boxes_f64(view, (int64_t)o.npix * o.ld, o.ld, J, jt, boxes, n, winsize_scale, momentum, boxes, jt + n, s);
+    if (rc != DH_OK) break;
+  }
+  if (rc != DH_OK) {
+    hipStreamSynchronize(s);                                           // nothing of this call stays in flight behind a refusal
+    return rc;
+  }
+  const size_t item_floats = o.npix * (size_t)o.C * (size_t)n;
+  bool ok = true;
+  for (int t = 0; ok && t < num_iter; ++t)
+    ok = hipMemcpyAsync(poses_out + (size_t)t * item_floats, poses + (size_t)t * pose_floats, item_floats * 4, hipMemcpyDeviceToHost, s) ==
+         hipSuccess;
+  ok = ok && hipMemcpyAsync(jobs_out, jobs, sizeof(dh_crop_job) * (size_t)n * T, hipMemcpyDeviceToHost, s) == hipSuccess;
+  ok = ok && hipMemcpyAsync(status_out, status, 4 * (size_t)n * T, hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return DH_ELAUNCH;
+  return DH_OK;
 }
 
 }  // extern "C"

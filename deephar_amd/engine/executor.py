@@ -1008,8 +1008,114 @@ class Executor:
         return [np.concatenate([r[k] for r in results], axis=0) if len(results) > 1 else results[0][k]
                 for k in range(nres)]
 
-    def run_device(self, tensors, n=None, inputs_copied=None):
+    def run_refine(self, store, index, bbox0, out_hw, outidx, num_iter, winsize_scale, momentum, bs, u8_norm):
         with self._lock:          # one thread at a time on the shared stream (engine/executor.py: stream_lock)
+            return self._run_refine_locked(store, index, bbox0, out_hw, outidx, num_iter, winsize_scale, momentum, bs, u8_norm)
+
+    def _run_refine_locked(self, store, index, bbox0, out_hw, outidx, num_iter, winsize_scale, momentum, bs, u8_norm):
+        """The box-refinement loop (evaltools.refine_pred_frames) with the boxes resident on the device: `num_iter` passes over
+        all N samples as num_iter x nchunks chunk-steps on the compute stream, iteration-major, with no host wait between the
+        first launch and the final drain other than the recycling of output slots.
+          once      : bbox0 (float64 [N, 4]) and the frame indices go to the device; dh_jobs_from_boxes_f64 makes iteration 0's
+                      slice of the job table int32 [num_iter, N, 6].
+          chunk-step: dh_crop_program_build_dev from the resident slice of the job table (per-job status into int32
+                      [num_iter, N]), dh_crop_resize_u8 into the plan's uint8 input, the forward, the packed-output D2H into
+                      the slot; then, but for the last iteration, dh_refine_boxes_f64 reads output `outidx` where it lies in
+                      the arena and writes the chunk's rows of the box table and of the next iteration's job table.
+          Iteration t + 1 of a chunk depends only on iteration t of the same chunk, and both are on this stream: no event.
+        One program buffer serves every chunk-step (its only reader is the crop launch right behind the builder).
+        Returns (raw output `outidx` per iteration: list of float32 [N, J, D]; the job tables int32 [num_iter, N, 6]; the
+        builder's status int32 [num_iter, N]).  A refused job leaves its input frame as the previous chunk-step left it."""
+        torch = _torch()
+        lib = _lib.load()
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        if len(self.plan.inputs) != 1 or u8_norm is None or tuple(self.plan.inputs[0].shape) != (OH, OW, 3):
+            raise ValueError('the device refinement loop feeds a single uint8 image input [%d, %d, 3]' % (OH, OW))
+        if not 0 <= outidx < len(self.plan.outputs) or len(self.plan.outputs[outidx].shape) != 2 or \
+                self.plan.outputs[outidx].shape[-1] < 2:
+            raise ValueError('output %d is no pose output [J, D >= 2]' % outidx)
+        index = np.ascontiguousarray(index, np.int32)
+        bbox0 = np.ascontiguousarray(bbox0, np.float64)
+        total = index.shape[0]
+        if bbox0.shape != (total, 4) or total < 1 or num_iter < 1:
+            raise ValueError('bbox0 %s does not give one box for each of %d samples' % (bbox0.shape, total))
+        if index.min() < 0 or index.max() >= len(store):
+            raise ValueError('frame index outside the %d stored frames' % len(store))
+        bs = int(min(bs, total))
+        nchunks = (total + bs - 1) // bs
+        vout = self.plan.outputs[outidx]
+        J = vout.shape[0]
+        with torch.cuda.device(self.device):
+            if self.bound:
+                self.sync_weights()
+            with torch.cuda.stream(self.stream):
+                bp = self.bind(bs, u8_norm=u8_norm)
+            if self._wstamp is None:
+                self._wstamp = self._weight_stamp()
+            depth = max(2, min(num_iter * nchunks, int(os.environ.get('DEEPHAR_PREDICT_DEPTH', '8'))))
+            io = self._io(bp, depth, staged=False)
+            nbytes = C.c_size_t(0)
+            rc = lib.dh_crop_program_max_bytes(bs, len(store), OH, OW, C.byref(nbytes))
+            if rc == -2:
+                raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % bs)
+            _lib.check(rc, 'dh_crop_program_max_bytes')
+            if io.get('refine_prog') is None or io['refine_prog'].numel() < nbytes.value:
+                io['refine_prog'] = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            prog = io['refine_prog']
+            srcs_dev = store.srcs_dev
+            io['pending'] = [None] * len(io['pending'])
+            results = []
+            pose = bp.tensor(vout)
+            dst = bp.u8[id(self.plan.inputs[0].buf)][0]
+
+            def collect(slot):
+                m = io['pending'][slot]
+                if m is not None:
+                    io['done'][slot].synchronize()
+                    results.append(self._host_outputs(bp, io['host_out'][slot], m)[outidx])
+                    io['pending'][slot] = None
+
+            try:
+                with torch.cuda.stream(self.stream):
+                    boxes = torch.from_numpy(bbox0).to(self.device, non_blocking=True)
+                    src = torch.from_numpy(index).to(self.device, non_blocking=True)
+                    jobs = torch.empty((num_iter, total, 6), dtype=torch.int32, device=self.device)
+                    status = torch.empty((num_iter, total), dtype=torch.int32, device=self.device)
+                    _lib.check(lib.dh_jobs_from_boxes_f64(boxes.data_ptr(), src.data_ptr(), total, jobs.data_ptr(), self.stream_ptr),
+                               'dh_jobs_from_boxes_f64')
+                    for step in range(num_iter * nchunks):
+                        t, ci = divmod(step, nchunks)
+                        slot, start = step % depth, ci * bs
+                        m = min(bs, total - start)
+                        collect(slot)                           # chunk-step `step - depth` used this slot
+                        _lib.check(lib.dh_crop_program_build_dev(
+                            srcs_dev.data_ptr(), len(store), jobs[t, start].data_ptr(), m, OH, OW, prog.data_ptr(), prog.numel(),
+                            status[t, start:].data_ptr(), self.stream_ptr), 'dh_crop_program_build_dev')
+                        _lib.check(lib.dh_crop_resize_u8(prog.data_ptr(), m, OH, OW, dst.data_ptr(), OH * OW * 3, self.stream_ptr),
+                                   'dh_crop_resize_u8')
+                        self.forward(bp)
+                        io['host_out'][slot].copy_(bp.arena[:io['host_out'][slot].numel()], non_blocking=True)
+                        io['done'][slot].record(self.stream)
+                        io['pending'][slot] = m
+                        if t + 1 < num_iter:                    # the chunk's next windows, from the poses in the arena
+                            _lib.check(lib.dh_refine_boxes_f64(
+                                pose.data_ptr(), pose.stride(0), pose.stride(1), J, jobs[t, start].data_ptr(),
+                                boxes[start].data_ptr(), m, float(winsize_scale), float(momentum), boxes[start].data_ptr(),
+                                jobs[t + 1, start].data_ptr(), self.stream_ptr), 'dh_refine_boxes_f64')
+                    jobs_host = jobs.cpu().numpy()              # one copy each, behind everything on the stream
+                    status_host = status.cpu().numpy()
+                for k in range(depth):                          # oldest pending chunk-step first
+                    collect((num_iter * nchunks + k) % depth)
+            finally:
+                if any(p is not None for p in io['pending']):
+                    self.stream.synchronize()
+                    io['pending'] = [None] * len(io['pending'])
+        raw = [np.concatenate(results[t * nchunks:(t + 1) * nchunks], axis=0) if nchunks > 1 else results[t * nchunks]
+               for t in range(num_iter)]
+        return raw, jobs_host, status_host
+
+    def run_device(self, tensors, n=None, inputs_copied=None):
+        with self._lock:         # one thread at a time on the shared stream (engine/executor.py: stream_lock)
             return self._run_device_locked(tensors, n, inputs_copied)
 
     def _run_device_locked(self, tensors, n=None, inputs_copied=None):

@@ -35,20 +35,32 @@ def refine_pred(model, frames, afmat, bbox, ds, mode, outidx, num_iter=2, winsiz
 
 
 def refine_pred_frames(model, frames, bbox0, outidx, num_iter=2, winsize_scale=1.50, momentum=0.8, batch_size=8,
-                       program='host'):
+                       program='host', loop='host'):
     """refine_pred over FULL frames: the same arithmetic, with the re-crop on the GPU (deephar_amd/frontend.py) instead of in
     a dataset.  `frames`: one uint8 [H, W, 3] image per sample (or a frontend.FrameStore), uploaded once for all iterations;
     `bbox0`: the initial float boxes [N, 4] -- what the dataset's `bbox` view shows before any custom box is set.  Every
     iteration crops window crop_box(*bbox_to_objposwin(box)) like the loader does (mpii.py:102-115), unflipped.  Returns
     the list of per-iteration poses in image coordinates.  `program` is predict_from_frames' keyword, passed on when it is
-    not the default."""
+    not the default.
+    loop='device': the boxes stay on the GPU between the iterations (frontend.refine_from_frames: dh_refine_boxes_f64 turns a
+    chunk's poses into its next windows right behind the forward, and the crop programs are built on the device, whatever
+    `program` says), so the whole run is one uninterrupted stream of launches; the image-space poses are computed here, on the
+    host, from every iteration's raw output and the windows it was cropped with, exactly as under loop='host'.  A window that
+    is empty or beyond the 16x scale cap raises the ValueError the host loop raises for it, naming the first iteration and
+    sample, after the run has drained."""
     from .. import frontend
+    if loop not in ('host', 'device'):
+        raise ValueError("loop must be 'host' or 'device', got %r" % (loop,))
     extra = {} if program == 'host' else {'program': program}
     if not isinstance(frames, frontend.FrameStore) and hasattr(model, 'executor'):
         frames = frontend.FrameStore(frames, model.executor.device)
     index = np.arange(len(bbox0))
     current = np.array(bbox0, dtype=np.float64).copy()
     out = []
+    if loop == 'device':
+        raws, windows, A = frontend.refine_from_frames(model, frames, index, current, outidx, num_iter=num_iter,
+                                                       winsize_scale=winsize_scale, momentum=momentum, batch_size=batch_size)
+        return [transform_pose_sequence(A[t].copy(), raws[t], inverse=True) for t in range(num_iter)]
     for t in range(num_iter):
         windows = np.stack([frontend.crop_box(*bbox_to_objposwin(b)) for b in current])
         res = frontend.predict_from_frames(model, frames, index, windows, batch_size=batch_size, **extra)

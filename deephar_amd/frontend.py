@@ -8,6 +8,8 @@ input of the bound plan; the result is bit for bit `model.predict(<the loader's 
 The launch reads a crop program (csrc/crop_index.h).  program='host' (the default) builds it on the host per chunk and copies
 it over; program='device' stages only the chunk's 24-byte jobs and builds the program on the GPU (dh_crop_program_build_dev,
 the same bytes), in front of the crop launch on the compute stream.
+refine_from_frames runs the whole box-refinement loop with the boxes resident on the device (dh_refine_boxes_f64 behind every
+forward, csrc/refine_index.h): the caller the device builder was made for.
 
 Scope: the loaders' test-mode geometry -- angle 0, integer window, bilinear, optional mirror, 3 channels, uint8.  Box and
 matrix bookkeeping stays on the host in float64 (crop_box, crop_afmat), composed like deephar/utils/transform.py does.
@@ -150,6 +152,40 @@ class CropFeed:
             raise ValueError('job staging too small')
         out[:nbytes].copy_(torch.from_numpy(part.reshape(-1).view(np.uint8)))
         return nbytes
+
+
+def refine_from_frames(model, frames, index, bbox0, outidx, num_iter=2, winsize_scale=1.50, momentum=0.8, batch_size=8):
+    """The box-refinement loop of evaltools.refine_pred_frames with the boxes resident on the GPU (Executor.run_refine): every
+    iteration's windows come from the previous iteration's poses through dh_refine_boxes_f64 and go straight into
+    dh_crop_program_build_dev; nothing visits the host between the first launch and the final drain.  Single-image models only.
+    Returns (raw output `outidx` per iteration, crop-normalised; the integer windows [num_iter, N, 4] every iteration
+    cropped; their crop_afmat maps [num_iter, N, 3, 3]).  ValueError, after the drain, for the first window the program builder
+    refused: the errors CropFeed raises on the host for the same window."""
+    if len(model.inputs) != 1:
+        raise ValueError('refine_from_frames needs a model with a single image input, %s has %d inputs' %
+                         (model.name, len(model.inputs)))
+    shape = tuple(model.inputs[0].shape)
+    if len(shape) != 3 or shape[-1] != 3:
+        raise ValueError('refine_from_frames needs a single-image input [H, W, 3], the model takes %s' % (shape,))
+    OH, OW = shape[0], shape[1]
+    ex = model.executor
+    store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
+    total = len(index)
+    bs = int(min(batch_size or total, total))
+    raws, jobs, status = ex.run_refine(store, index, bbox0, (OH, OW), outidx, num_iter, winsize_scale, momentum, bs,
+                                       model.channel_power)
+    bad = np.argwhere(status != 0)
+    if len(bad):
+        t, i = (int(v) for v in bad[0])
+        if status[t, i] == -2:
+            raise ValueError('a crop window is more than 16 times its output on one axis (or the output row does not fit LDS): '
+                             'iteration %d, sample %d, window %s' % (t, i, jobs[t, i, 1:5].tolist()))
+        raise ValueError('empty crop box: iteration %d, sample %d, window %s' % (t, i, jobs[t, i, 1:5].tolist()))
+    windows = jobs[:, :, 1:5].astype(np.int64)
+    afmat = np.zeros((num_iter, total, 3, 3))
+    for pos in np.ndindex(num_iter, total):
+        afmat[pos] = crop_afmat(windows[pos], (OW, OH), False)
+    return raws, windows, afmat
 
 
 def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32, program='host'):

@@ -208,6 +208,57 @@ def crop_resize(sources, jobs, out_hw, out=None, item_pitch=None, program='host'
     return y
 
 
+def _refine_tables(boxes, jobs=None, src=None):
+    torch = _t()
+    if not (boxes.is_cuda and boxes.dtype == torch.float64 and boxes.dim() == 2 and boxes.shape[1] == 4 and boxes.is_contiguous()):
+        raise ValueError('boxes must be a contiguous float64 CUDA tensor [n, 4]')
+    n = boxes.shape[0]
+    if jobs is not None and not (jobs.is_cuda and jobs.dtype == torch.int32 and tuple(jobs.shape) == (n, 6) and jobs.is_contiguous()):
+        raise ValueError('jobs must be a contiguous int32 CUDA tensor [%d, 6] (src, x0, y0, x1, y1, hflip)' % n)
+    if src is not None and not (src.is_cuda and src.dtype == torch.int32 and tuple(src.shape) == (n,) and src.is_contiguous()):
+        raise ValueError('src must be a contiguous int32 CUDA tensor [%d]' % n)
+    return n
+
+
+def jobs_from_boxes(boxes, src, out=None):
+    """Crop jobs from float boxes on the GPU (dh_jobs_from_boxes_f64): boxes float64 [n, 4], src int32 [n] (frame indices).
+    Returns int32 [n, 6] rows (src, x0, y0, x1, y1, 0) with the window frontend.crop_box(*bbox_to_objposwin(b)) -- corners
+    truncated toward zero; a box whose corners are not finite int32 values gives the empty job (src, 0, 0, 0, 0, 0)."""
+    torch = _t()
+    n = _refine_tables(boxes, src=src)
+    jobs = torch.empty((n, 6), dtype=torch.int32, device=boxes.device) if out is None else out
+    _refine_tables(boxes, jobs=jobs)
+    rc = _lib.load().dh_jobs_from_boxes_f64(_p(boxes), _p(src), n, _p(jobs), _stream())
+    if rc == -1:
+        raise ValueError('jobs_from_boxes: bad argument (no samples)')
+    _lib.check(rc, 'dh_jobs_from_boxes_f64')
+    return jobs
+
+
+def refine_boxes(poses, jobs, boxes, winsize_scale=1.5, momentum=0.8, out_boxes=None, out_jobs=None):
+    """One pose -> box step of the box-refinement loop on the GPU (dh_refine_boxes_f64), on torch's current stream.
+    poses: float32 CUDA [n, J, D >= 2] in crop-normalised coordinates, any sample and joint strides with a unit channel stride
+    (a view of a plan's output is read where it lies); jobs int32 [n, 6]: the windows the poses were predicted in; boxes
+    float64 [n, 4]: the float boxes those windows came from.  Returns (new boxes, new jobs); out_boxes / out_jobs may be the
+    inputs themselves (in place)."""
+    torch = _t()
+    n = _refine_tables(boxes, jobs=jobs)
+    if not (poses.is_cuda and poses.dtype == torch.float32 and poses.dim() == 3 and poses.shape[0] == n and poses.shape[2] >= 2 and
+            (poses.stride(2) == 1)):
+        raise ValueError('poses must be a float32 CUDA tensor [%d, J, D >= 2] with a unit channel stride' % n)
+    nb = torch.empty_like(boxes) if out_boxes is None else out_boxes
+    nj = torch.empty_like(jobs) if out_jobs is None else out_jobs
+    _refine_tables(nb, jobs=nj)
+    J = poses.shape[1]
+    sample_stride = poses.stride(0) if n > 1 else max(poses.stride(0), (J - 1) * poses.stride(1) + 2)
+    rc = _lib.load().dh_refine_boxes_f64(_p(poses), sample_stride, poses.stride(1) if J > 1 else max(poses.stride(1), 2), J,
+                                         _p(jobs), _p(boxes), n, float(winsize_scale), float(momentum), _p(nb), _p(nj), _stream())
+    if rc == -1:
+        raise ValueError('refine_boxes: bad argument (no samples, no joints, or strides smaller than the extent they span)')
+    _lib.check(rc, 'dh_refine_boxes_f64')
+    return nb, nj
+
+
 def dwconv2d(x, dw_kernel, pre_scale=None, pre_shift=None, pre_relu=False, up_in=False):
     """Depthwise conv, stride 1, TF-SAME.  dw_kernel numpy [kh,kw,C,1].  up_in: x is at half resolution and the
     convolution runs on UpSampling2D((2, 2))(x) without writing it out (dh_dw_args.up_in)."""

@@ -509,6 +509,7 @@ int dh_plan_num_outputs(const dh_plan* plan);
 int64_t dh_plan_input_items(const dh_plan* plan, int i);  /* elements (floats, or bytes of a uint8 input) per batch item */
 int dh_plan_input_is_u8(const dh_plan* plan, int i);      /* 1: input i takes raw uint8 frames, 0: float32, -1: no such input */
 int64_t dh_plan_output_items(const dh_plan* plan, int i); /* floats per batch item of output i */
+int dh_plan_output_channels(const dh_plan* plan, int i);  /* its last dimension (D of a pose output [J, D]); -1: no such output */
 int dh_forward(dh_plan* plan, const float* const* inputs_dev, int m, float* const* outputs_dev, void* stream);
 int dh_forward_host(dh_plan* plan, const float* const* inputs_host, int m, float* const* outputs_host);
 /* The device address dh_forward copies input i to (float inputs; NULL for a uint8 input or no such input).  A caller that
@@ -730,6 +731,53 @@ int dh_forward_frames(dh_plan* plan, const dh_frames* f, const dh_crop_job* jobs
                       float* const* outputs_dev, void* stream);
 int dh_forward_frames_host(dh_plan* plan, const dh_frames* f, const dh_crop_job* jobs_host, int njobs, int OH, int OW,
                            float* const* outputs_host);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Box refinement on the device: the pose -> box -> re-crop loop of the MPII evaluation (exp/common/mpii_tools.py:13-52 in
+ * the reference, deephar_amd/evaltools/bbox.py: refine_pred_frames) with the boxes resident in device memory -- the caller
+ * dh_crop_program_build_dev was made for.  The arithmetic is csrc/refine_index.h, in double, never fused, the same bits on
+ * the host (`_host` twins over host pointers) and on the device.
+ *   window of a float box b = (bx0, by0, bx2, by2) -- crop_box(*bbox_to_objposwin(b)): cx = (bx0 + bx2) / 2, w = bx2 - bx0
+ *            (cy, h likewise); corners cx - w/2, cy - h/2, cx + w/2, cy + h/2, each truncated toward zero to int32.  A corner
+ *            that is not finite or of magnitude >= 2^31 makes the job the EMPTY job (src, 0, 0, 0, 0, 0), which the program
+ *            builders refuse (DH_EINVAL) and dh_crop_program_build_dev skips.
+ *   jobs_from_boxes: jobs[i] = (src[i], window of boxes[4 i .. 4 i + 3], hflip 0), one lane per sample.
+ *   refine_boxes: per sample i, from job (src, x0, y0, x1, y1, hflip), box b and the J joints (u_j, v_j) of its pose in
+ *            crop-normalised coordinates (float32 at poses[i * sample_stride + j * joint_stride + {0, 1}], strides in floats:
+ *            the launch reads a plan's output where it lies in the arena): cw = x1 - x0, ch = y1 - y0; ulo, uhi, vlo, vhi the
+ *            min / max over the joints; lx = x0 + ulo cw, hx = x0 + uhi cw, ly = y0 + vlo ch, hy = y0 + vhi ch; p = the
+ *            centre of that extent; side = winsize_scale max(hx - lx, hy - ly); t = the centre of b; o = momentum t +
+ *            (1 - momentum) p; the new box is o -+ side / 2 and the new job its window with the same src, unflipped.  An input
+ *            job that is flipped or empty yields the empty job and passes its box through; a NaN joint coordinate makes the
+ *            box NaN (every NaN leaves as the one quiet NaN 0x7ff8000000000000) and the job empty.  Joints are not filtered.
+ *            One wavefront per sample, lanes over the joints, cross-lane min / max (exact: no order dependence), lane 0 does
+ *            the doubles.  boxes_out / jobs_out may alias the inputs.  No atomics; nothing allocates, nothing synchronises.
+ *   DH_EINVAL: NULL (or misaligned device) pointers, n < 1, J < 1, joint_stride < 2, sample_stride < (J - 1) joint_stride + 2.
+ *   refine_frames_host: the whole num_iter-pass loop of ONE batch (n <= dh_plan_batch) from a C host: src (frame indices into
+ *            `f`) and boxes0 (float64 [n, 4]) are uploaded once; per iteration dh_crop_program_build_dev from the resident job
+ *            table (status kept per job), dh_crop_resize_u8 into the plan's input, the forward, and -- but for the last --
+ *            dh_refine_boxes_f64 on output `outidx` in the arena, all on the plan's internal stream with ONE synchronisation
+ *            at the end.  poses_out [num_iter, n, J, D] are the RAW outputs (crop-normalised; the image-space poses follow on
+ *            the host from jobs_out), jobs_out [num_iter, n] the windows every iteration cropped, status_out [num_iter, n] the
+ *            builder's codes (a refused job leaves its input frame as the previous iteration left it).
+ *   refine_frames_shape: the refusals of refine_frames_host on their own, GPU-free: more than one input, a float input, a clip
+ *            plan (input_items != OH * OW * 3), n outside [1, batch], num_iter < 1, outidx outside [0, num_outputs), an output
+ *            of fewer than two channels (out_channels: dh_plan_output_channels; out_items: dh_plan_output_items).  Answers J.
+ * ------------------------------------------------------------------------------------------------- */
+int dh_jobs_from_boxes_f64(const double* boxes, const int32_t* src, int n, dh_crop_job* jobs, void* stream);
+int dh_jobs_from_boxes_host(const double* boxes, const int32_t* src, int n, dh_crop_job* jobs);
+int dh_refine_boxes_f64(const float* poses, int64_t sample_stride, int64_t joint_stride, int J, const dh_crop_job* jobs_in,
+                        const double* boxes_in, int n, double winsize_scale, double momentum, double* boxes_out,
+                        dh_crop_job* jobs_out, void* stream);
+int dh_refine_boxes_host(const float* poses, int64_t sample_stride, int64_t joint_stride, int J, const dh_crop_job* jobs_in,
+                         const double* boxes_in, int n, double winsize_scale, double momentum, double* boxes_out,
+                         dh_crop_job* jobs_out);
+int dh_refine_frames_shape(int num_inputs, int input_is_u8, int64_t input_items, int batch, int n, int OH, int OW, int num_outputs,
+                           int outidx, int64_t out_items, int out_channels, int num_iter, int* J);
+int dh_refine_frames_host(dh_plan* plan, const dh_frames* f, const int32_t* src, const double* boxes0, int n, int OH, int OW,
+                          int outidx, int num_iter, double winsize_scale, double momentum,
+                          float* poses_out /* [num_iter, n, J, D] raw */, dh_crop_job* jobs_out /* [num_iter, n] */,
+                          int32_t* status_out /* [num_iter, n] */);
 
 /* ---------------------------------------------------------------------------------------------------
  * Stream-ordered runtime helpers (no torch types): graphs for launch-bound replay, events for timing.
