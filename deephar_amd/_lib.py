@@ -97,6 +97,11 @@ class ClipInfo(C.Structure):                     # == struct dh_clip_info (dh_cl
                [(n, C.c_uint64) for n in ('frames_offset', 'frames_bytes', 'head_offset', 'head_bytes')]
 
 
+class PlanInfo(C.Structure):                     # == struct dh_plan_info (dh_plan_inspect)
+    _fields_ = [(n, i32) for n in ('version', 'batch', 'num_inputs', 'num_outputs', 'num_steps', 'nstreams', 'num_ops',
+                                   'num_events')] + [(n, C.c_uint64) for n in ('arena_bytes', 'weight_bytes', 'byte_bytes')]
+
+
 # dh_allgather_fn: (ctx, send, recv, floats per rank, stream) -> 0 on success
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, vp, vp, vp, i64, vp)
 
@@ -117,6 +122,16 @@ def sam_route(lib, args, J=0, nctx=0):
     r = SamRoute()
     assert lib.dh_softargmax2d_route(C.byref(args), J, nctx, C.byref(r)) == 0
     return r
+
+
+def plan_record(lib, fn):
+    """dh_plan_record as (entry point name, first blob version, payload bytes, [pointer offsets]); None outside the table."""
+    name, first, size, n = C.c_char_p(), C.c_int(), C.c_size_t(), C.c_int()
+    offs = (i32 * 32)()
+    if lib.dh_plan_record(fn, C.byref(name), C.byref(first), C.byref(size), offs, len(offs), C.byref(n)) != 0:
+        return None
+    assert n.value <= len(offs)
+    return name.value.decode(), first.value, size.value, list(offs[:n.value])
 
 
 # name -> (restype, argtypes); every symbol include/deephar_hip.h declares
@@ -177,6 +192,9 @@ SIGNATURES = {
     'dh_plan_input_ptr': (vp, [vp, C.c_int]),
     'dh_plan_num_streams': (C.c_int, [vp]),
     'dh_plan_side_stream': (vp, [vp, C.c_int]),
+    'dh_plan_inspect': (C.c_int, [vp, C.c_size_t, C.POINTER(PlanInfo)]),
+    'dh_plan_record': (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(i32), C.c_int,
+                                 C.POINTER(C.c_int)]),
     'dh_pack_outputs_f32': (C.c_int, [C.POINTER(OutSeg), C.c_int, vp]),
     'dh_pack_outputs_host': (C.c_int, [C.POINTER(OutSeg), C.c_int]),
     'dh_pack_outputs_vec4': (C.c_int, [C.c_int, C.c_int, vp, vp]),

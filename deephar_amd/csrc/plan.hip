@@ -2,7 +2,8 @@
 // "a plan/execute pair over device pointers ... one plan per device; stream-ordered, no internal threads".
 // The blob is written by deephar_amd/engine/serialize.py (format documented there) from a bound, autotuned plan: the
 // launch list of Model.predict with every device pointer expressed relative to the activation arena or the weight
-// image.  This file owns the two allocations, patches the pointers once and replays the launches in order on the
+// image.  The blob's format lives in plan_blob.h (GPU-free: the step-record table, the parser, the patch loop); this file
+// owns the allocations, patches the pointers once and replays the launches in order on the
 // caller's stream -- the same C-ABI entry points the Python executor calls, so the results are the same bits.  A version-5
 // blob carries the engine's multi-stream schedule: plan_sched.h (GPU-free) turns it into the enqueue program of
 // BoundPlan.launch_all, which dh_forward runs with the caller's stream as stream 0 and the plan's own side streams.  Every
@@ -12,19 +13,17 @@
 #include <cstring>
 #include <vector>
 #include "dh_kernels.h"
-#include "plan_sched.h"
+#include "plan_blob.h"
 #include "crop_index.h"
 #include "refine_index.h"
 
 namespace {
 
-using dh::check_launch;
+using namespace dh;             // enum Fn, kRecords, PlanImage
+using Out = PlanOut;
 
-enum Fn { F_CONV, F_DW, F_POOL, F_UPADD, F_ELT, F_SAM, F_CTX, F_DMEANS, F_SAM1D, F_KRON, F_GMM, F_COPY, F_ZPAD, F_DFM, F_SAMCTX, F_NORM, F_GROUP, F_PAIR, F_SEG, F_DWS, F_CONVT, F_CONVTS, F_COUNT };
-
-struct Step { int fn; std::vector<unsigned char> payload; };
-struct In { uint64_t tag; size_t items; int u8; char* dst; };   // dst: where dh_forward copies the caller's data (patched)
-struct Out { size_t off, npix; int C, ld; };
+struct Step { int fn; std::vector<unsigned char> payload; };    // a copy of the blob's record, its pointers patched
+struct In { size_t items; int u8; char* dst; };                 // dst: where dh_forward copies the caller's data (patched)
 // floats output o of `items` batch items takes in dh_forward_host's staging buffer: rounded up to whole 16-byte runs
 inline size_t stage_floats(const Out& o, int items) { return (o.npix * (size_t)o.C * (size_t)items + 3) & ~(size_t)3; }
 
@@ -32,7 +31,6 @@ inline size_t stage_floats(const Out& o, int items) { return (o.npix * (size_t)o
 
 struct dh_plan {
   int n = 0;
-  size_t arena_bytes = 0, weight_bytes = 0, byte_bytes = 0;
   char* arena = nullptr;
   char* weights = nullptr;
   char* bytes = nullptr;        // region 3: uint8 input staging of a uint8-input plan
@@ -71,84 +69,6 @@ struct dh_frames {
 };
 
 namespace {
-
-struct Reader {
-  const unsigned char* p;
-  const unsigned char* end;
-  bool ok = true;
-  template <typename T>
-  T get() {
-    T v{};
-    if (p + sizeof(T) > end) { ok = false; return v; }
-    std::memcpy(&v, p, sizeof(T));
-    p += sizeof(T);
-    return v;
-  }
-};
-
-// (region << 60) | offset -> device pointer; false when the offset leaves its region
-bool fix(const dh_plan& pl, uint64_t v, void** out) {
-  const uint64_t region = v >> 60, off = v & ((1ull << 60) - 1);
-  if (v == 0) { *out = nullptr; return true; }
-  if (region == 1 && off < pl.arena_bytes) { *out = pl.arena + off; return true; }
-  if (region == 2 && off < pl.weight_bytes) { *out = pl.weights + off; return true; }
-  if (region == 3 && off < pl.byte_bytes) { *out = pl.bytes + off; return true; }
-  return false;
-}
-
-// leading pointer fields of the argument structs (include/deephar_hip.h)
-int struct_pointers(int fn) {
-  switch (fn) {
-    case F_CONV: return 10;
-    case F_DW: return 5;
-    case F_POOL: return 2;
-    case F_ELT: return 6;
-    case F_SAM: return 8;
-    case F_SAMCTX: return 8;
-    case F_DWS: return 5;
-    case F_CONVT: return 6;
-    case F_CONVTS: return 6;
-  }
-  return -1;
-}
-// u64 arguments that follow the struct, and which of them are pointers
-void struct_extra(int fn, int* nargs, unsigned* ptr_mask) {
-  *nargs = 0;
-  *ptr_mask = 0;
-  if (fn == F_CONV || fn == F_CONVT) *nargs = 1;                 // tile_cfg
-  if (fn == F_CONVTS) *nargs = 2;                                // parts, tile_cfg
-  if (fn == F_SAMCTX) { *nargs = 5; *ptr_mask = 0x08; }           // J, nctx, agg_alpha, y, ldy
-}
-size_t struct_size(int fn) {
-  switch (fn) {
-    case F_CONV: return sizeof(dh_conv_args);
-    case F_DW: return sizeof(dh_dw_args);
-    case F_POOL: return sizeof(dh_pool_args);
-    case F_ELT: return sizeof(dh_elt_args);
-    case F_SAM: return sizeof(dh_sam_args);
-    case F_SAMCTX: return sizeof(dh_sam_args);
-    case F_DWS: return sizeof(dh_dw_strided);
-    case F_CONVT: return sizeof(dh_conv_transpose);
-    case F_CONVTS: return sizeof(dh_conv_transpose);
-  }
-  return 0;
-}
-// number of u64 arguments of the scalar-argument entry points, and which of them are pointers (bit mask)
-bool scalar_sig(int fn, int* nargs, unsigned* ptr_mask) {
-  switch (fn) {
-    case F_UPADD: *nargs = 10; *ptr_mask = 0x15; return true;         // a, lda, b, ldb, y, ldy, N, H, W, C
-    case F_CTX: *nargs = 9; *ptr_mask = 0x0f; return true;            // ys, yc, pc, y, F, J, nctx, alpha, ldy
-    case F_DMEANS: *nargs = 8; *ptr_mask = 0x0d; return true;         // h, ldh, hxy, hz, F, HW, D, J
-    case F_SAM1D: *nargs = 8; *ptr_mask = 0x17; return true;          // hz, grid, z, ldz, vz, F, D, J
-    case F_KRON: *nargs = 10; *ptr_mask = 0x15; return true;          // hm, ldh, x, ldx, f, ldf, B, P, J, C
-    case F_GMM: *nargs = 7; *ptr_mask = 0x05; return true;            // x, ldx, y, B, P, C, softmax
-    case F_COPY: *nargs = 6; *ptr_mask = 0x05; return true;           // x, ldx, y, ldy, npix, C
-    case F_ZPAD: *nargs = 10; *ptr_mask = 0x03; return true;          // x, y, B, H, W, C, OH, OW, PT, PL
-    case F_DFM: *nargs = 9; *ptr_mask = 0x15; return true;            // d, ldd, h, ldh, z, ldz, F, HW, J
-    case F_NORM: *nargs = 5; *ptr_mask = 0x07; return true;           // x (bytes), lut, y, n_pixels, C
-  }
-  return false;
-}
 
 int run_step(const Step& st, void* stream) {
   const unsigned char* p = st.payload.data();
@@ -216,177 +136,58 @@ int run_step(const Step& st, void* stream) {
 
 extern "C" {
 
+int dh_plan_inspect(const void* blob, size_t bytes, dh_plan_info* out) {
+  PlanImage im;
+  if (out == nullptr) return DH_EINVAL;
+  const int rc = plan_parse(blob, bytes, &im);
+  if (rc == DH_OK) *out = im.info;
+  return rc;
+}
+
+int dh_plan_record(int fn, const char** name, int* first_version, size_t* payload_bytes, int32_t* offsets, int max_offsets,
+                   int* num_offsets) {
+  if (fn < 0 || fn >= F_COUNT || name == nullptr || first_version == nullptr || payload_bytes == nullptr || num_offsets == nullptr ||
+      max_offsets < 0 || (max_offsets > 0 && offsets == nullptr))
+    return DH_EINVAL;
+  const Record& rec = kRecords[fn];
+  *name = rec.name;
+  *first_version = (int)rec.first_version;
+  *payload_bytes = rec.bytes;
+  *num_offsets = (int)rec.nptr;
+  for (int k = 0; k < max_offsets && k < (int)rec.nptr; ++k) offsets[k] = rec.ptr[k];
+  return DH_OK;
+}
+
+// every malformed blob is refused (DH_EINVAL) before the first allocation; DH_ELAUNCH is a failed HIP call on a well-formed one
 int dh_plan_create(const void* blob, size_t blob_bytes, dh_plan** out) {
-  if (blob == nullptr || out == nullptr || blob_bytes < 44) return DH_EINVAL;
-  Reader r{static_cast<const unsigned char*>(blob), static_cast<const unsigned char*>(blob) + blob_bytes};
-  if (std::memcmp(r.p, "DHPL", 4) != 0) return DH_EINVAL;
-  r.p += 4;
-  const uint32_t version = r.get<uint32_t>();
-  // version 3 = version 2 + the step records of dh_dwconv2d_strided_f32 / dh_conv2d_transpose2x2_f32 (function ids 19, 20)
-  // version 4 = version 3 + the step record of dh_conv2d_transpose2x2_split_f32 (function id 21)
-  // version 5 = version 4 + a schedule section between the steps and the weight image (multi-stream plans)
-  if (version < 1 || version > 5) return DH_EINVAL;
+  PlanImage im;
+  if (out == nullptr || plan_parse(blob, blob_bytes, &im) != DH_OK) return DH_EINVAL;
   dh_plan* pl = new dh_plan();
-  pl->n = r.get<int32_t>();
-  pl->arena_bytes = r.get<uint64_t>();
-  pl->weight_bytes = r.get<uint64_t>();
-  const uint32_t nin = r.get<uint32_t>(), nout = r.get<uint32_t>(), nsteps = r.get<uint32_t>();
-  if (version >= 2) pl->byte_bytes = r.get<uint64_t>();
   auto fail = [&](int rc) { dh_plan_destroy(pl); return rc; };
-  if (!r.ok || pl->n <= 0 || nin == 0 || nout == 0 || nin > 64 || nout > 4096 || nsteps > (1u << 20) ||
-      pl->byte_bytes > (1ull << 40))
-    return fail(DH_EINVAL);
-  for (uint32_t i = 0; i < nin; ++i) {
-    In in{};
-    in.tag = r.get<uint64_t>();
-    in.items = (size_t)r.get<uint64_t>();
-    if (version >= 2) {
-      in.u8 = (int)r.get<uint32_t>();
-      (void)r.get<uint32_t>();
-    } else {
-      in.tag |= 1ull << 60;        // version 1 stored the bare arena offset
-    }
-    pl->ins.push_back(in);
-  }
-  for (uint32_t i = 0; i < nout; ++i) {
-    Out o;
-    o.off = r.get<uint64_t>(); o.npix = r.get<uint64_t>(); o.C = (int)r.get<uint32_t>(); o.ld = (int)r.get<uint32_t>();
-    pl->outs.push_back(o);
-  }
-  for (uint32_t i = 0; i < nsteps && r.ok; ++i) {
-    Step st;
-    st.fn = (int)r.get<uint32_t>();
-    const uint32_t nb = r.get<uint32_t>();
-    if (!r.ok || st.fn < 0 || st.fn >= (version >= 4 ? (int)F_COUNT : (version == 3 ? (int)F_CONVTS : (int)F_DWS)) || r.p + nb > r.end) return fail(DH_EINVAL);
-    st.payload.assign(r.p, r.p + nb);
-    r.p += nb;
+  const dh_plan_info& h = im.info;
+  pl->n = h.batch;
+  if (hipMalloc(&pl->arena, h.arena_bytes ? h.arena_bytes : 16) != hipSuccess) return fail(DH_ELAUNCH);
+  if (hipMalloc(&pl->weights, h.weight_bytes ? h.weight_bytes : 16) != hipSuccess) return fail(DH_ELAUNCH);
+  if (h.weight_bytes && hipMemcpy(pl->weights, im.weights, h.weight_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(DH_ELAUNCH);
+  if (h.byte_bytes && hipMalloc(&pl->bytes, h.byte_bytes) != hipSuccess) return fail(DH_ELAUNCH);
+  for (const PlanIn& in : im.ins)           // float inputs land in the arena, uint8 frames in region 3
+    pl->ins.push_back(In{(size_t)in.items, in.u8, (in.u8 ? pl->bytes : pl->arena) + (in.tag & kPlanOffMask)});
+  pl->outs = im.outs;
+  // copy the step records and patch their pointers (once)
+  for (const PlanStep& ps : im.steps) {
+    Step st{ps.fn, std::vector<unsigned char>(ps.payload, ps.payload + ps.bytes)};
+    if (plan_patch(st.payload.data(), kRecords[ps.fn], pl->arena, pl->weights, pl->bytes) != DH_OK) return fail(DH_EINVAL);
     pl->steps.push_back(std::move(st));
   }
-  int nstreams = 1, nevents = 0;
-  if (version >= 5) {
-    // schedule section: u32 nstreams | u32 npre | u32 #entries | u32 #waits | per entry u32 step (0xffffffff: no launch),
-    // u32 stream, u32 flags (bit 0: records an event), u32 #waits of the entry | the waits, entry by entry.  Validated and
-    // turned into the enqueue program by plan_sched.h; only the host is touched here.
-    const uint32_t ns = r.get<uint32_t>(), npre = r.get<uint32_t>(), nent = r.get<uint32_t>(), nwaits = r.get<uint32_t>();
-    if (!r.ok || nent > (uint32_t)dh::kSchedMaxEntries || ns > 0x7fffffffu || npre > nent ||
-        (uint64_t)(r.end - r.p) < 16ull * nent || (uint64_t)(r.end - r.p) - 16ull * nent < 4ull * nwaits)
-      return fail(DH_EINVAL);
-    std::vector<int32_t> step(nent), stream(nent), record(nent), wait_off(nent + 1, 0), waits(nwaits);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < nent; ++i) {
-      step[i] = (int32_t)r.get<uint32_t>();
-      const uint32_t s = r.get<uint32_t>(), flags = r.get<uint32_t>(), nw = r.get<uint32_t>();
-      if (s >= ns || flags > 1 || (total += nw) > nwaits) return fail(DH_EINVAL);
-      stream[i] = (int32_t)s;
-      record[i] = (int32_t)flags;
-      wait_off[i + 1] = (int32_t)total;
-    }
-    if (total != nwaits) return fail(DH_EINVAL);
-    for (uint32_t k = 0; k < nwaits; ++k) waits[k] = (int32_t)r.get<uint32_t>();
-    const dh::SchedTable tab = {(int)nent, step.data(), stream.data(), record.data(), wait_off.data(), waits.data(), (int)nwaits,
-                                (int)ns, (int)npre, (int)pl->steps.size()};
-    dh::SchedProgram prog;
-    if (!r.ok || dh::sched_build(tab, &prog) != DH_OK) return fail(DH_EINVAL);
-    pl->ops.swap(prog.ops);
-    nstreams = (int)ns;
-    nevents = prog.nevents;
-  }
-  if (!r.ok || (size_t)(r.end - r.p) != pl->weight_bytes) return fail(DH_EINVAL);
-  if (hipMalloc(&pl->arena, pl->arena_bytes ? pl->arena_bytes : 16) != hipSuccess) return fail(DH_ELAUNCH);
-  if (hipMalloc(&pl->weights, pl->weight_bytes ? pl->weight_bytes : 16) != hipSuccess) return fail(DH_ELAUNCH);
-  if (pl->weight_bytes && hipMemcpy(pl->weights, r.p, pl->weight_bytes, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(DH_ELAUNCH);
-  if (pl->byte_bytes && hipMalloc(&pl->bytes, pl->byte_bytes) != hipSuccess) return fail(DH_ELAUNCH);
-  // extents, overflow-safe: every factor is bounded by the arena size (in floats) before it is multiplied.  The blob is
-  // trusted, code-equivalent input (it carries launch arguments); these checks catch truncation and mix-ups, they are
-  // not a sandbox.
-  const uint64_t arena_f = pl->arena_bytes / 4, nn = (uint64_t)pl->n;
-  auto fits = [&](uint64_t off_bytes, uint64_t rows, uint64_t pitch, uint64_t last) {   // off + ((rows-1)*pitch + last)*4
-    if (off_bytes % 4 || off_bytes / 4 > arena_f || rows == 0 || pitch > arena_f || last > arena_f || rows > arena_f) return false;
-    const uint64_t room = arena_f - off_bytes / 4;
-    if (pitch != 0 && rows - 1 > room / pitch) return false;
-    return (rows - 1) * pitch + last <= room;
-  };
-  for (In& in : pl->ins) {
-    const uint64_t region = in.tag >> 60, off = in.tag & ((1ull << 60) - 1);
-    if (in.u8 == 0) {
-      if (region != 1 || in.items == 0 || in.items > arena_f || !fits(off, nn, in.items, in.items)) return fail(DH_EINVAL);
-      in.dst = pl->arena + off;
-    } else {                       // uint8 frames land in region 3
-      if (in.u8 != 1 || region != 3 || in.items == 0 || in.items > pl->byte_bytes || nn > pl->byte_bytes / in.items ||
-          off > pl->byte_bytes - in.items * nn)
-        return fail(DH_EINVAL);
-      in.dst = pl->bytes + off;
-    }
-  }
-  for (const Out& o : pl->outs)
-    if (o.C <= 0 || o.ld < o.C || o.npix == 0 || o.npix > arena_f || !fits(o.off, o.npix * nn, (uint64_t)o.ld, (uint64_t)o.C))
-      return fail(DH_EINVAL);
-  // patch the pointers (once)
-  for (Step& st : pl->steps) {
-    const int np = struct_pointers(st.fn);
-    if (st.fn == F_GROUP || st.fn == F_PAIR || st.fn == F_SEG) {   // dh_conv_args followed by dh_dw_args (dh_conv2d_dw_group_f32) / by a
-                                                   // second dh_conv_args (dh_conv2d_pair_f32) / by dh_conv_seg (dh_conv2d_seg_f32)
-      const size_t second = st.fn == F_GROUP ? sizeof(dh_dw_args) : (st.fn == F_PAIR ? sizeof(dh_conv_args) : sizeof(dh_conv_seg));
-      if (st.payload.size() != sizeof(dh_conv_args) + second) return fail(DH_EINVAL);
-      size_t at_off[10 + 1 + 10 + 1];
-      int k = 0;
-      for (int i = 0; i < 10; ++i) at_off[k++] = (size_t)8 * i;
-      at_off[k++] = offsetof(dh_conv_args, y_pool);
-      for (int i = 0; i < (st.fn == F_GROUP ? 5 : (st.fn == F_PAIR ? 10 : 1)); ++i) at_off[k++] = sizeof(dh_conv_args) + (size_t)8 * i;
-      if (st.fn == F_PAIR) at_off[k++] = sizeof(dh_conv_args) + offsetof(dh_conv_args, y_pool);
-      for (int i = 0; i < k; ++i) {
-        unsigned char* at = st.payload.data() + at_off[i];
-        uint64_t v;
-        void* ptr;
-        std::memcpy(&v, at, 8);
-        if (!fix(*pl, v, &ptr)) return fail(DH_EINVAL);
-        std::memcpy(at, &ptr, 8);
-      }
-    } else if (np >= 0) {
-      int nextra;
-      unsigned emask;
-      struct_extra(st.fn, &nextra, &emask);
-      if (st.payload.size() != struct_size(st.fn) + (size_t)nextra * 8) return fail(DH_EINVAL);
-      if (st.fn == F_CONV) {                     // (y_pool sits behind the integer fields of dh_conv_args)
-        unsigned char* at = st.payload.data() + offsetof(dh_conv_args, y_pool);
-        uint64_t v;
-        void* ptr;
-        std::memcpy(&v, at, 8);
-        if (!fix(*pl, v, &ptr)) return fail(DH_EINVAL);
-        std::memcpy(at, &ptr, 8);
-      }
-      for (int i = 0; i < np + nextra; ++i) {
-        if (i >= np && !(emask & (1u << (i - np)))) continue;
-        unsigned char* at = st.payload.data() + (i < np ? (size_t)8 * i : struct_size(st.fn) + (size_t)8 * (i - np));
-        uint64_t v;
-        void* ptr;
-        std::memcpy(&v, at, 8);
-        if (!fix(*pl, v, &ptr)) return fail(DH_EINVAL);
-        std::memcpy(at, &ptr, 8);
-      }
-    } else {
-      int nargs;
-      unsigned mask;
-      if (!scalar_sig(st.fn, &nargs, &mask) || st.payload.size() != (size_t)nargs * 8) return fail(DH_EINVAL);
-      for (int i = 0; i < nargs; ++i)
-        if (mask & (1u << i)) {
-          uint64_t v;
-          void* ptr;
-          std::memcpy(&v, st.payload.data() + 8 * i, 8);
-          if (!fix(*pl, v, &ptr)) return fail(DH_EINVAL);
-          std::memcpy(st.payload.data() + 8 * i, &ptr, 8);
-        }
-    }
-  }
+  pl->ops.swap(im.ops);
   // a multi-stream plan's own streams and events: nstreams - 1 non-blocking streams (sched_build bounds nstreams by 4: the
   // hardware queues of a process), fork + joins + one event per recording entry + relays
-  for (int k = 1; k < nstreams; ++k) {
+  for (int k = 1; k < im.info.nstreams; ++k) {
     hipStream_t st = nullptr;
     if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return fail(DH_ELAUNCH);
     pl->side.push_back(st);
   }
-  for (int e = 0; e < nevents; ++e) {
+  for (int e = 0; e < im.info.num_events; ++e) {
     hipEvent_t ev = nullptr;
     if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(DH_ELAUNCH);
     pl->events.push_back(ev);
@@ -557,20 +358,25 @@ int fetch_outputs(dh_plan* pl, float* const* outputs_host, int m, size_t used) {
   return DH_OK;
 }
 
+// a device buffer of the plan that only grows: `*have` elements of `elem` bytes now, at least `need` afterwards.  A failure
+// leaves no buffer (the next call tries again).  (hipFree waits for the device: a forward still reading the old one finishes first)
+template <typename T>
+int grow(T** buf, size_t* have, size_t need, size_t elem) {
+  if (*have >= need) return DH_OK;
+  if (*buf) hipFree(*buf);
+  *buf = nullptr;
+  *have = 0;
+  if (hipMalloc(reinterpret_cast<void**>(buf), need * elem) != hipSuccess) return DH_ELAUNCH;
+  *have = need;
+  return DH_OK;
+}
+
 // the plan's device crop program, large enough for a FULL batch over the frames of `f`: one allocation per plan
 int crop_program_room(dh_plan* pl, const dh_frames* f, int per_item, int OH, int OW) {
   size_t need = 0;
   const int rc = dh_crop_program_max_bytes(pl->n * per_item, (int)f->px.size(), OH, OW, &need);
   if (rc != DH_OK) return rc;
-  if (pl->crop_prog_bytes < need) {
-    // (hipFree waits for the device: a forward still reading the old program finishes first)
-    if (pl->crop_prog) hipFree(pl->crop_prog);
-    pl->crop_prog = nullptr;
-    pl->crop_prog_bytes = 0;
-    if (hipMalloc(&pl->crop_prog, need) != hipSuccess) return DH_ELAUNCH;
-    pl->crop_prog_bytes = need;
-  }
-  return DH_OK;
+  return grow(&pl->crop_prog, &pl->crop_prog_bytes, need, 1);
 }
 
 // dh_forward_frames_shape of this plan: the items `njobs` crops of OH x OW x 3 bytes fill and the frames per item, or DH_EINVAL
@@ -679,13 +485,8 @@ int dh_forward_frames_host(dh_plan* pl, const dh_frames* f, const dh_crop_job* j
   rc = host_staging(pl);
   if (rc != DH_OK) return rc;
   const size_t full = (size_t)pl->n * (size_t)per_item;
-  if (pl->crop_jobs_n < full) {
-    if (pl->crop_jobs) hipFree(pl->crop_jobs);
-    pl->crop_jobs = nullptr;
-    pl->crop_jobs_n = 0;
-    if (hipMalloc(&pl->crop_jobs, full * sizeof(dh_crop_job)) != hipSuccess) return DH_ELAUNCH;
-    pl->crop_jobs_n = full;
-  }
+  rc = grow(&pl->crop_jobs, &pl->crop_jobs_n, full, sizeof(dh_crop_job));
+  if (rc != DH_OK) return rc;
   if (hipMemcpyAsync(pl->crop_jobs, jobs_host, (size_t)njobs * sizeof(dh_crop_job), hipMemcpyHostToDevice, pl->stream) != hipSuccess)
     return DH_ELAUNCH;
   const size_t used = place_outputs(pl, outputs_host, m);
@@ -718,13 +519,8 @@ int dh_refine_frames_host(dh_plan* pl, const dh_frames* f, const int32_t* src, c
   const size_t off_jobs = up16(32 * N), off_status = off_jobs + up16(sizeof(dh_crop_job) * N * T);
   const size_t off_src = off_status + up16(4 * N * T), off_poses = off_src + up16(4 * N);
   const size_t need = off_poses + pose_floats * 4 * T;
-  if (pl->refine_bytes < need) {
-    if (pl->refine_buf) hipFree(pl->refine_buf);
-    pl->refine_buf = nullptr;
-    pl->refine_bytes = 0;
-    if (hipMalloc(&pl->refine_buf, need) != hipSuccess) return DH_ELAUNCH;
-    pl->refine_bytes = need;
-  }
+  rc = grow(&pl->refine_buf, &pl->refine_bytes, need, 1);
+  if (rc != DH_OK) return rc;
   double* boxes = reinterpret_cast<double*>(pl->refine_buf);
   dh_crop_job* jobs = reinterpret_cast<dh_crop_job*>(pl->refine_buf + off_jobs);
   int32_t* status = reinterpret_cast<int32_t*>(pl->refine_buf + off_status);

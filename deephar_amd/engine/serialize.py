@@ -110,17 +110,62 @@ def _is_ptr_type(t):
     return t is C.c_void_p
 
 
-def _scalars(sig, args, reg):
+def _is_struct_ptr(t):
+    return isinstance(getattr(t, '_type_', None), type) and issubclass(t._type_, C.Structure)
+
+
+def _scalars(sig, args, tag):
     assert len(sig) == len(args), (len(sig), len(args))
     parts = []
     for t, a in zip(sig, args):
         if _is_ptr_type(t):
-            parts.append(struct.pack('<Q', reg.tag(a)))
+            parts.append(struct.pack('<Q', tag(a)))
         elif t is C.c_float:
             parts.append(struct.pack('<fI', float(a), 0))
         else:
             parts.append(struct.pack('<q', int(a)))
     return b''.join(parts)
+
+
+def pack_steps(launches, tag):
+    """-> [bytes]: the step record of every launch (module docstring).  launches: [(entry point name, [argument structs],
+    [the arguments behind them, without the stream])], as engine/binding.py binds them; tag(ptr) -> the tagged pointer
+    (region << 60) | byte offset of a non-null address.  Pointer fields and pointer arguments are the c_void_p ones of the
+    ctypes structs and of _lib.SIGNATURES (csrc/plan_blob.h holds the reader's table; tests/test_plan_blob_host.py compares
+    the two).  No device needed."""
+    names = {n: i for i, n in enumerate(ALL_FUNCTIONS)}
+    steps = []
+    for name, structs, scalars in launches:
+        if name not in names:
+            raise ValueError('%s has no serialised form' % name)
+        payload = b''
+        for obj in structs:                                   # (dh_conv2d_dw_group_f32 takes two structs)
+            raw = bytearray(bytes(obj))
+            for fname, ftype in obj._fields_:
+                if _is_ptr_type(ftype):
+                    off = getattr(type(obj), fname).offset
+                    raw[off:off + 8] = struct.pack('<Q', tag(getattr(obj, fname) or 0))
+            payload += bytes(raw)
+        sig = _lib.SIGNATURES[name][1][len(structs):-1]      # without the structs in front and the stream behind
+        payload += _scalars(sig, scalars, lambda p: tag(p or 0))
+        steps.append(struct.pack('<II', names[name], len(payload)) + payload)
+    return steps
+
+
+def pack_plan(batch, arena_bytes, inputs, outputs, launches, tag, weights=b'', u8_bytes=0, section=b''):
+    """-> bytes: a plan blob (module docstring).  inputs: [(address of the buffer dh_forward copies to, elements per batch
+    item, dtype 0 float32 / 1 uint8)]; outputs: [(arena byte offset, pixels per batch item, channels, pixel pitch)];
+    launches, tag: as for pack_steps; weights: the weight image, or a callable that returns it once every pointer has gone
+    through `tag` (the exporter lays the image out as `tag` meets its tensors); section: the schedule section (pack_schedule)
+    of a version-5 blob.  No device needed."""
+    steps = pack_steps(launches, tag)
+    ins = b''.join(struct.pack('<QQII', tag(ptr), int(items), int(dtype), 0) for ptr, items, dtype in inputs)
+    outs = b''.join(struct.pack('<QQII', int(off), int(npix), int(c), int(ld)) for off, npix, c, ld in outputs)
+    image = bytes(weights() if callable(weights) else weights)
+    version = plan_version((struct.unpack_from('<I', st)[0] for st in steps), section)
+    head = MAGIC + struct.pack('<IiQQIIIQ', version, int(batch), int(arena_bytes), len(image), len(inputs), len(outputs),
+                               len(steps), int(u8_bytes))
+    return head + ins + outs + b''.join(steps) + section + image
 
 
 def blob_version(function_ids):
@@ -182,55 +227,38 @@ def dump_plan(model, batch, u8_norm=None, multi_stream=False):
             ex.sync_weights()
         bp = ex.bind(batch, u8_norm=u8_norm)
     ex.stream.synchronize()
+    # the device half: the bound calls as (entry point, structs, scalars), the three regions, the weight image read back
     lib = _lib.load()
-    names = {n: i for i, n in enumerate(ALL_FUNCTIONS)}
     by_addr = {C.cast(getattr(lib, n), C.c_void_p).value: n for n in ALL_FUNCTIONS}
     reg = _Regions(bp)
-    steps = []
+    launches = []
     for idx, (fn, args, step) in enumerate(bp.calls):
         if idx in bp.noop_calls:                              # merged into an earlier launch (BoundPlan.group_launches)
             continue
         name = by_addr.get(C.cast(fn, C.c_void_p).value)
         if name is None:
             raise ValueError('step %s (%s) has no serialised form' % (step.kind, step.name))
-        sig = _lib.SIGNATURES[name][1][:-1]                 # without the trailing stream
-        if len(sig) and isinstance(getattr(sig[0], '_type_', None), type) and issubclass(sig[0]._type_, C.Structure):
-            payload, nstruct = b'', 0
-            while nstruct < len(sig) and isinstance(getattr(sig[nstruct], '_type_', None), type) and \
-                    issubclass(sig[nstruct]._type_, C.Structure):     # (dh_conv2d_dw_group_f32 takes two structs)
-                obj = args[nstruct]._obj
-                raw = bytearray(bytes(obj))
-                for fname, ftype in obj._fields_:
-                    if _is_ptr_type(ftype):
-                        off = getattr(type(obj), fname).offset
-                        raw[off:off + 8] = struct.pack('<Q', reg.tag(getattr(obj, fname)))
-                payload += bytes(raw)
-                nstruct += 1
-            payload += _scalars(sig[nstruct:], args[nstruct:], reg)
-        else:
-            payload = _scalars(sig, args, reg)
-        steps.append(struct.pack('<II', names[name], len(payload)) + payload)
+        nstruct = sum(1 for t in _lib.SIGNATURES[name][1] if _is_struct_ptr(t))     # (the argument structs come first, by reference)
+        launches.append((name, [a._obj for a in args[:nstruct]], args[nstruct:]))
     plan = bp.plan
+    if bp.u8 is not None:
+        inputs = [(bp.u8[id(v.buf)][0].data_ptr(), int(np.prod(v.shape)), 1) for v in plan.inputs]
+    else:
+        inputs = [(bp.ptr(v), int(np.prod(v.shape)), 0) for v in plan.inputs]
+    if any(v.coff % 1 or v.ld < v.C for v in plan.outputs):
+        raise ValueError('output view not serialisable')
+    outputs = [(bp.ptr(v) - bp.base, v.npix, v.C, v.ld) for v in plan.outputs]
+
+    def image():
+        raw = bytearray((reg.size + 255) & ~255)
+        for off, t in reg.image:
+            b = t.detach().cpu().contiguous().numpy().tobytes()
+            raw[off:off + len(b)] = b
+        return raw
+
     section = schedule_section([c[2] for c in bp.calls], plan.nstreams, bp.npre, bp.noop_calls, multi_stream)
-    version = plan_version((struct.unpack_from('<I', st)[0] for st in steps), section)
-    head = MAGIC + struct.pack('<IiQQIIIQ', version, bp.n, bp.arena.numel() * 4, (reg.size + 255) & ~255,
-                               len(plan.inputs), len(plan.outputs), len(steps), reg.u8_size)
-    ins = b''
-    for v in plan.inputs:
-        if bp.u8 is not None:
-            ins += struct.pack('<QQII', reg.tag(bp.u8[id(v.buf)][0].data_ptr()), int(np.prod(v.shape)), 1, 0)
-        else:
-            ins += struct.pack('<QQII', reg.tag(bp.ptr(v)), int(np.prod(v.shape)), 0, 0)
-    outs = b''
-    for v in plan.outputs:
-        if v.coff % 1 or v.ld < v.C:
-            raise ValueError('output view not serialisable')
-        outs += struct.pack('<QQII', bp.ptr(v) - bp.base, v.npix, v.C, v.ld)
-    image = bytearray((reg.size + 255) & ~255)
-    for off, t in reg.image:
-        b = t.detach().cpu().contiguous().numpy().tobytes()
-        image[off:off + len(b)] = b
-    return head + ins + outs + b''.join(steps) + section + bytes(image)
+    # the pure half
+    return pack_plan(bp.n, bp.arena.numel() * 4, inputs, outputs, launches, reg.tag, image, reg.u8_size, section)
 
 
 CLIP_MAGIC, CLIP_VERSION = b'DHCL', 1

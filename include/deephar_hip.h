@@ -521,6 +521,23 @@ int dh_plan_num_streams(const dh_plan* plan);             /* streams a forward r
 /* test aid, like dh_stream_spin_us: the plan's own side stream k (1 <= k < dh_plan_num_streams), so a test can delay it
  * against the caller's stream; NULL for any other k.  The handle belongs to the plan. */
 void* dh_plan_side_stream(const dh_plan* plan, int k);
+/* The plan blob on its own, GPU-free (csrc/plan_blob.h; dh_plan_create parses with exactly this before it allocates).
+ *   inspect: every check of dh_plan_create that needs no device -- magic, version, header limits, the input and output
+ *            tables and their extents, every step record (an id the blob's version knows, the payload size of that id, every
+ *            tagged pointer inside its region), the schedule section, "the rest is the weight image".  Every malformed or
+ *            truncated blob is DH_EINVAL; nothing is allocated on a device.  num_ops / num_events: the enqueue program of a
+ *            version-5 blob and the events it needs (0 / 0 and nstreams 1 below version 5).
+ *   record : the step record of function id `fn` (the index into serialize.ALL_FUNCTIONS): the entry point dh_forward calls,
+ *            the first blob version that knows the id, the payload bytes, and the byte offsets of the payload's pointer slots
+ *            (*num_offsets of them; at most max_offsets are written to `offsets`, which may be NULL).  DH_EINVAL outside the
+ *            table.  The writer packs from the ctypes signatures; tests/test_plan_blob_host.py holds the two against each other. */
+typedef struct dh_plan_info {
+  int32_t version, batch, num_inputs, num_outputs, num_steps, nstreams, num_ops, num_events;
+  uint64_t arena_bytes, weight_bytes, byte_bytes;   /* regions 1, 2, 3 of the tagged pointers */
+} dh_plan_info;
+int dh_plan_inspect(const void* blob, size_t bytes, dh_plan_info* out);
+int dh_plan_record(int fn, const char** name, int* first_version, size_t* payload_bytes, int32_t* offsets, int max_offsets,
+                   int* num_offsets);
 
 /* ---------------------------------------------------------------------------------------------------
  * Every wanted output of a forward in one launch: the counterpart of dh_unpack_cut_f32 at the other end.  dh_forward ends

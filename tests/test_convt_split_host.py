@@ -112,7 +112,7 @@ def test_eligibility_is_a_rule_on_geometry_and_alignment(hip_lib):
 
 
 # ---- serialisation -----------------------------------------------------------------------------------------------------
-def test_function_table_appends_the_split_entry_point_as_version_4():
+def test_function_table_appends_the_split_entry_point_as_version_4(hip_lib):
     from deephar_amd.engine import serialize as S
     assert S.ALL_FUNCTIONS[:21] == S.FUNCTIONS[:21] and len(S.FUNCTIONS) == 21
     assert S.FUNCTIONS[:21] == [
@@ -125,11 +125,11 @@ def test_function_table_appends_the_split_entry_point_as_version_4():
     assert new == 21 and len(S.ALL_FUNCTIONS) == 22
     assert S.blob_version([0, 1, new, 20]) == 4                            # the new id makes version 4 ...
     assert S.blob_version([0, 19, 20]) == 3 and S.blob_version([0, 4, 18]) == 2 and S.blob_version([]) == 2   # ... nothing else does
-    # the C executor's table has the same order
+    # the C executor's table has the same order, and the same versions (dh_plan_record: csrc/plan_blob.h)
     from deephar_amd import _lib
-    src = open(os.path.join(_lib._HERE, 'csrc', 'plan.hip')).read()
-    enum = re.search(r'enum Fn \{([^}]*)\}', src).group(1).replace(' ', '').split(',')
-    assert enum[20:] == ['F_CONVT', 'F_CONVTS', 'F_COUNT'] and len(enum) == len(S.ALL_FUNCTIONS) + 1
+    records = [_lib.plan_record(hip_lib, fn) for fn in range(len(S.ALL_FUNCTIONS))]
+    assert [r[0] for r in records] == S.ALL_FUNCTIONS and _lib.plan_record(hip_lib, len(S.ALL_FUNCTIONS)) is None
+    assert [r[1] for r in records[18:]] == [1, 3, 3, 4] and {r[1] for r in records[:19]} == {1}
 
 
 def test_the_ctypes_signature_serialises_as_struct_plus_two_integers():

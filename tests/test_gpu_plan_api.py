@@ -55,6 +55,16 @@ def test_c_plan_reproduces_predict_bit_for_bit(kind, hip_lib, cuda, tmp_path):
         assert hip_lib.dh_plan_num_outputs(plan) == len(ref)
         assert hip_lib.dh_plan_input_items(plan, 0) == x[0].size
         assert [hip_lib.dh_plan_output_items(plan, k) for k in range(len(ref))] == [r[0].size for r in ref]
+        # the GPU-free inspection of the same bytes agrees with the created plan
+        from deephar_amd import _lib
+        info = _lib.PlanInfo()
+        assert hip_lib.dh_plan_inspect(blob, len(blob), C.byref(info)) == 0
+        assert (info.batch, info.num_inputs, info.num_outputs, info.nstreams) == \
+            (hip_lib.dh_plan_batch(plan), hip_lib.dh_plan_num_inputs(plan), hip_lib.dh_plan_num_outputs(plan), hip_lib.dh_plan_num_streams(plan))
+        assert info.version == blob[4] and info.byte_bytes == 0 and hip_lib.dh_plan_input_is_u8(plan, 0) == 0
+        bp = m.executor.bound[n]
+        assert info.num_steps == len(bp.calls) - len(bp.noop_calls) and info.arena_bytes == bp.arena.numel() * 4
+        assert (info.num_ops, info.num_events) == (0, 0) and len(blob) > info.weight_bytes > 0
         # device pointers, caller's stream
         xd = torch.from_numpy(x).to(cuda)
         outs = [torch.full(r.shape, float('nan'), device=cuda) for r in ref]
