@@ -156,6 +156,7 @@ SIGNATURES = {
     'dh_conv2d_f32': (C.c_int, [C.POINTER(ConvArgs), C.c_int, vp]),
     'dh_normalize_u8_f32': (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp]),
     'dh_dwconv2d_f32': (C.c_int, [C.POINTER(DwArgs), vp]),
+    'dh_dwconv2d_uses_lds_kernel': (C.c_int, [C.POINTER(DwArgs)]),
     'dh_dwconv2d_strided_f32': (C.c_int, [C.POINTER(DwsArgs), vp]),
     'dh_conv2d_transpose2x2_num_tile_cfgs': (C.c_int, []),
     'dh_conv2d_transpose2x2_f32': (C.c_int, [C.POINTER(ConvtArgs), C.c_int, vp]),

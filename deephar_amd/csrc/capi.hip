@@ -171,6 +171,8 @@ int dh_dwconv2d_f32(const dh_dw_args* a, void* stream) {
   return launch_dwconv(*a, S(stream));
 }
 
+int dh_dwconv2d_uses_lds_kernel(const dh_dw_args* a) { return a != nullptr && dwconv_uses_lds(*a) ? 1 : 0; }
+
 int dh_dwconv2d_strided_f32(const dh_dw_strided* a, void* stream) {
   if (a == nullptr || a->x == nullptr || a->w == nullptr || a->y == nullptr) return DH_EINVAL;
   if ((a->pre_scale == nullptr) != (a->pre_shift == nullptr)) return DH_EINVAL;

@@ -32,6 +32,7 @@ int launch_conv_splitk(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
 int launch_conv_stem(const ConvArgs& a, const ConvRoute& r, hipStream_t s);
 int launch_normalize_u8(const unsigned char* x, const float* lut, float* y, long long n_pixels, int C, hipStream_t s);
 int launch_dwconv(const DwArgs& a, hipStream_t s);
+bool dwconv_uses_lds(const DwArgs& a);      // launch_dwconv takes the LDS-tiled kernel (dw_lds.h: dw_lds_geometry)
 int launch_dwconv_strided(const DwsArgs& a, hipStream_t s);
 int launch_convt2x2(const ConvArgs& gemm, int cb, int cfg, hipStream_t s);
 int convt2x2_num_cfgs();

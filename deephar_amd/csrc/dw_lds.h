@@ -246,7 +246,8 @@ struct DwLdsGeom {
 inline bool dw_lds_geometry(const DwArgs& a, DwLdsGeom& g) {
   const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && al16(a.x) && al16(a.y) && al16(a.w) &&
                    (a.pre_scale == nullptr || (al16(a.pre_scale) && al16(a.pre_shift)));
-  if (!(vec && a.KH == a.KW && (a.KW == 5 || a.KW == 3) && a.C % 32 == 0 && a.W >= DW_LDS_MIN_W && a.W % 8 == 0)) return false;
+  if (!(vec && a.KH == a.KW && (a.KW == 5 || a.KW == 3) && a.C % 32 == 0 && a.W >= DW_LDS_MIN_W && a.W % 8 == 0 && a.H >= 1))
+    return false;
   g.tw = a.W >= 32 ? 32 : a.W;
   g.nt = g.tw == 8 ? 64 : 256;
   g.rows = g.nt / (8 * (g.tw / 8));
@@ -254,7 +255,15 @@ inline bool dw_lds_geometry(const DwArgs& a, DwLdsGeom& g) {
   const long long blocks = (long long)a.N * ((a.W + g.tw - 1) / g.tw) * (a.C / 32);    // bands are walked inside
   g.lds = ((size_t)(g.rows + a.KW - 1) * (g.tw + a.KW - 1) * DW_PITCH + (size_t)a.KW * a.KW * DW_CQ + 1) * 16;
   const bool fits31 = (long long)a.H * a.W * a.ldx * 4 < 0x7fffffffLL && (long long)a.H * a.W * a.ldy * 4 < 0x7fffffffLL;
-  if (blocks > 0x7fffffffLL || !fits31) return false;
+  // The window rows above and below the frame are read at 32-bit offsets that must stay out of the descriptor's range: row
+  // -PT as a negative int (>= -2^31), the last row of the last band (up to KS - 2 - PT rows behind the frame) below 2^32.
+  // With 'same' padding and two rows or more fits31 implies both; a one-row map with a pitch near the bound does not (the
+  // rows behind it wrap past 2^32 into the frame), nor does a caller's larger PT.
+  const int ush = a.up_in ? 1 : 0;
+  const long long row_bytes = (long long)(a.W >> ush) * a.ldx * 4;
+  const long long last_row = (long long)((a.H + g.rows - 1) / g.rows) * g.rows + a.KH - 2 - a.PT;
+  const bool halo32 = ((last_row >> ush) + 1) * row_bytes <= 0x100000000LL && (((long long)a.PT + ush) >> ush) * row_bytes <= 0x80000000LL;
+  if (blocks > 0x7fffffffLL || !fits31 || !halo32) return false;
   g.blocks = (unsigned)blocks;
   // slots per thread: 256 threads = 32 tile pixels per slot (5 x 36-pixel rows above, 8 x 36 or 16 x 20 new pixels per
   // band), 64 threads = 8 pixels per slot (4 x 12 above, 8 x 12 new)

@@ -336,6 +336,10 @@ __global__ __launch_bounds__(256) void zeropad_kernel(const float* __restrict__ 
   }
 }
 
+// The kernels form a pixel's index from int products (n * H + h, then 64-bit): every tensor of a launch holds at most
+// 2^31 - 1 pixels, as the convolutions require (conv_check_geometry)
+inline bool pixels_fit31(long long n, long long h, long long w) { return h >= 0 && w >= 0 && n * h <= 0x7fffffffLL && n * h * w <= 0x7fffffffLL; }
+
 inline unsigned grid_for(long long total, int block = 256) {
   long long g = (total + block - 1) / block;
   const long long cap = 256LL * 16;  // 256 CUs x 16 workgroups, grid-stride beyond that
@@ -378,28 +382,23 @@ int launch_dw_lds(const DwArgs& a, int tw, int rows, int nt, unsigned blocks, si
 
 }  // namespace
 
+bool dwconv_uses_lds(const DwArgs& a) {
+  DwLdsGeom g;
+  return a.N > 0 && a.C > 0 && a.KH > 0 && a.KW > 0 && !(a.up_in && ((a.H & 1) || (a.W & 1))) && pixels_fit31(a.N, a.H, a.W) &&
+         dw_lds_geometry(a, g);
+}
+
 int launch_dwconv(const DwArgs& a, hipStream_t s) {
   if (a.N <= 0 || a.C <= 0 || a.KH <= 0 || a.KW <= 0) return DH_EINVAL;
   if (a.up_in && ((a.H & 1) || (a.W & 1))) return DH_EINVAL;        // an up-sampled input has even extents
+  if (!pixels_fit31(a.N, a.H, a.W)) return DH_EINVAL;
   const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && al16(a.x) && al16(a.y) &&
                    al16(a.w) && (a.pre_scale == nullptr || (al16(a.pre_scale) && al16(a.pre_shift)));
-  if (vec && a.KH == a.KW && (a.KW == 5 || a.KW == 3) && a.C % 32 == 0 && a.W >= DW_LDS_MIN_W && a.W % 8 == 0) {
-    // LDS-tiled path: column tile = min(W, 32), 8-column strips; the work-group is sized to the map --
-    //   W >= 32: 256 threads = 8 channel quads x 4 strips x 8 rows, bands of 8 rows walked inside the work-group
-    //   W == 16: 256 threads x 16 rows, one band (128 threads x 8 rows, two bands, 38 KB of LDS: 19.4 vs 18.0 us, not used)
-    //   W ==  8:  64 threads x  8 rows: the whole 8 x 8 map of a 32-channel chunk in one band (10.7 us; the register
-    //             kernel these maps ran on before took 13.0)
-    const int tw = a.W >= 32 ? 32 : a.W;
-    const int nt = tw == 8 ? 64 : 256;
-    int rows = nt / (8 * (tw / 8));
-    if (rows > a.H) rows = a.H;                                      // (8 or 16, or the even H of an up-sampled input: even)
-    const long long blocks = (long long)a.N * ((a.W + tw - 1) / tw) * (a.C / 32);    // bands are walked inside
-    const size_t lds = ((size_t)(rows + a.KW - 1) * (tw + a.KW - 1) * DW_PITCH + (size_t)a.KW * a.KW * DW_CQ + 1) * 16;
-    const bool fits31 = (long long)a.H * a.W * a.ldx * 4 < 0x7fffffffLL && (long long)a.H * a.W * a.ldy * 4 < 0x7fffffffLL;
-    if (blocks <= 0x7fffffffLL && fits31) {
-      const int rc = launch_dw_lds(a, tw, rows, nt, (unsigned)blocks, lds, s);
-      if (rc != DH_EUNSUPPORTED) return rc;
-    }
+  // LDS-tiled path where dw_lds_geometry (dw_lds.h: the one rule, dh_dwconv2d_uses_lds_kernel exports it) takes the layer
+  DwLdsGeom g;
+  if (dw_lds_geometry(a, g)) {
+    const int rc = launch_dw_lds(a, g.tw, g.rows, g.nt, g.blocks, g.lds, s);
+    if (rc != DH_EUNSUPPORTED) return rc;
   }
   if (vec && a.KH == a.KW && (a.KW == 5 || a.KW == 3 || a.KW == 1)) {
     const int TW = a.W >= 16 ? 8 : 4;
@@ -422,6 +421,7 @@ int launch_dwconv_strided(const DwsArgs& a, hipStream_t s) {
   if (a.N <= 0 || a.C <= 0 || a.H <= 0 || a.W <= 0 || a.OH <= 0 || a.OW <= 0 || a.PT < 0 || a.PL < 0 || a.ldx < a.C ||
       a.ldy < a.C)
     return DH_EINVAL;
+  if (!pixels_fit31(a.N, a.H, a.W) || !pixels_fit31(a.N, a.OH, a.OW)) return DH_EINVAL;
   if (!(a.KH == a.KW && (a.KW == 3 || a.KW == 5) && a.SH == 2 && a.SW == 2)) return DH_EUNSUPPORTED;
   // every window starts inside the padded frame: the last one may hang over the bottom / right edge (zero padding)
   if ((a.OH - 1) * a.SH - a.PT >= a.H || (a.OW - 1) * a.SW - a.PL >= a.W) return DH_EINVAL;
@@ -442,6 +442,7 @@ int launch_dwconv_strided(const DwsArgs& a, hipStream_t s) {
 
 int launch_pool(const PoolArgs& a, hipStream_t s) {
   if (a.N <= 0 || a.C <= 0 || a.OH <= 0 || a.OW <= 0) return DH_EINVAL;
+  if (!pixels_fit31(a.N, a.H, a.W) || !pixels_fit31(a.N, a.OH, a.OW)) return DH_EINVAL;
   const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (a.ldy % 4 == 0) && al16(a.x) && al16(a.y);
   const long long total = (long long)a.N * a.OH * a.OW * (vec ? a.C / 4 : a.C);
   if (vec) hipLaunchKernelGGL(pool_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, a);
@@ -451,7 +452,7 @@ int launch_pool(const PoolArgs& a, hipStream_t s) {
 
 int launch_upsample2x_add(const float* a, int lda, const float* b, int ldb, float* y, int ldy, int N, int H,
                           int W, int C, hipStream_t s) {
-  if (N <= 0 || C <= 0 || (H & 1) || (W & 1)) return DH_EINVAL;
+  if (N <= 0 || C <= 0 || (H & 1) || (W & 1) || !pixels_fit31(N, H, W)) return DH_EINVAL;
   const bool vec = (C % 4 == 0) && (ldb % 4 == 0) && (ldy % 4 == 0) && al16(b) && al16(y) &&
                    (a == nullptr || ((lda % 4 == 0) && al16(a)));
   const long long total = (long long)N * H * W * (vec ? C / 4 : C);
@@ -483,7 +484,7 @@ int launch_copy_channels(const float* x, int ldx, float* y, int ldy, long long n
 
 int launch_zeropad(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int PT, int PL,
                    hipStream_t s) {
-  if (B <= 0 || C <= 0 || PT < 0 || PL < 0 || OH < H + PT || OW < W + PL) return DH_EINVAL;
+  if (B <= 0 || C <= 0 || PT < 0 || PL < 0 || OH < H + PT || OW < W + PL || !pixels_fit31(B, OH, OW)) return DH_EINVAL;
   hipLaunchKernelGGL(zeropad_kernel, dim3(grid_for((long long)B * OH * OW * C)), dim3(256), 0, s, x, y, B, H, W, C,
                      OH, OW, PT, PL);
   return check_launch();

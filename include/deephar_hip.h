@@ -232,6 +232,10 @@ typedef struct dh_dw_args {
                     occupies what was tail padding of the struct: a caller that zero-initialises it is unchanged */
 } dh_dw_args;
 int dh_dwconv2d_f32(const dh_dw_args* a, void* stream);
+/* 1 when dh_dwconv2d_f32 runs this launch on its LDS-tiled kernel (32-bit buffer offsets inside a frame), 0 when on a
+ * register kernel (64-bit addresses) or not at all.  Every field filled in as for the launch; no pointer is dereferenced.
+ * All stride-1 kernels sum in one order: the answer never changes a bit of the result. */
+int dh_dwconv2d_uses_lds_kernel(const dh_dw_args* a);
 
 /* ---------------------------------------------------------------------------------------------------
  * Strided depthwise KxK conv: the depthwise half of keras SeparableConv2D(k, strides=(2, 2), padding='same',
