@@ -222,6 +222,10 @@ SIGNATURES = {
     'dh_refine_boxes_host': (C.c_int, [vp, i64, i64, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp]),
     'dh_refine_frames_shape': (C.c_int, [C.c_int, C.c_int, i64] + [C.c_int] * 6 + [i64, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'dh_refine_frames_host': (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5 + [C.c_double, C.c_double, vp, vp, vp]),
+    'dh_pose_boxes_f64': (C.c_int, [vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp, i64, C.c_int, C.c_double, vp, vp, vp, vp]),
+    'dh_pose_boxes_host': (C.c_int, [vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp, i64, C.c_int, C.c_double, vp, vp, vp]),
+    'dh_frame_boxes_shape': (C.c_int, [C.c_int, C.c_int, i64] + [C.c_int] * 6 + [i64, C.c_int, C.POINTER(C.c_int)]),
+    'dh_frame_boxes_host': (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 4 + [C.c_double, vp, vp, vp]),
     'dh_sched_build_ops':(C.c_int, [C.c_int] + [C.POINTER(i32)] * 5 + [C.c_int] * 4 + [C.POINTER(SchedOp), C.c_int,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dh_unpack_cut_f32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int, vp]),

@@ -16,6 +16,7 @@
 #include "plan_blob.h"
 #include "crop_index.h"
 #include "refine_index.h"
+#include "posebox_index.h"
 
 namespace {
 
@@ -60,6 +61,10 @@ struct dh_plan {
   // builder's status of every iteration, the frame indices and the raw poses of every iteration, in ONE allocation
   char* refine_buf = nullptr;
   size_t refine_bytes = 0;
+  // dh_frame_boxes_host (allocated on first use): the float64 boxes, the int32 boxes and the status words of a full batch
+  char* boxes_buf = nullptr;
+  size_t boxes_bytes = 0;
+  std::vector<dh_crop_job> boxes_jobs;                                 // the host job table of the call in flight
 };
 
 // full frames resident on the device: dense rows (pitch 3 * W), one allocation per frame, and the source table of the launch
@@ -212,6 +217,7 @@ int dh_plan_destroy(dh_plan* pl) {
   if (pl->crop_prog) hipFree(pl->crop_prog);
   if (pl->crop_jobs) hipFree(pl->crop_jobs);
   if (pl->refine_buf) hipFree(pl->refine_buf);
+  if (pl->boxes_buf) hipFree(pl->boxes_buf);
   delete pl;
   return DH_OK;
 }
@@ -561,6 +567,64 @@ int dh_refine_frames_host(dh_plan* pl, const dh_frames* f, const int32_t* src, c
          hipSuccess;
   ok = ok && hipMemcpyAsync(jobs_out, jobs, sizeof(dh_crop_job) * (size_t)n * T, hipMemcpyDeviceToHost, s) == hipSuccess;
   ok = ok && hipMemcpyAsync(status_out, status, 4 * (size_t)n * T, hipMemcpyDeviceToHost, s) == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return DH_ELAUNCH;
+  return DH_OK;
+}
+
+// ---- the per-frame person-box pass of one batch: only the boxes and their status leave the device ---------------------------------
+int dh_frame_boxes_host(dh_plan* pl, const dh_frames* f, const int32_t* src, const int32_t* windows, int n, int OH, int OW, int outidx,
+                        double relsize, int32_t* boxes_out, double* boxes_f64_out, int32_t* status_out) {
+  if (pl == nullptr || f == nullptr || src == nullptr || windows == nullptr || boxes_out == nullptr || boxes_f64_out == nullptr ||
+      status_out == nullptr || pl->ins.size() != 1 || outidx < 0 || outidx >= (int)pl->outs.size())
+    return DH_EINVAL;
+  const Out& o = pl->outs[(size_t)outidx];
+  int J = 0;
+  int rc = dh::frame_boxes_shape((int)pl->ins.size(), pl->ins[0].u8, (int64_t)pl->ins[0].items, pl->n, n, OH, OW, (int)pl->outs.size(),
+                                 outidx, (int64_t)(o.npix * (size_t)o.C), o.C, &J);
+  if (rc != DH_OK) return rc;
+  std::vector<dh_crop_job>& jobs_host = pl->boxes_jobs;                // (outlives the upload: ONE synchronisation, at the end)
+  jobs_host.resize((size_t)n);
+  for (int i = 0; i < n; ++i)
+    jobs_host[(size_t)i] = dh_crop_job{src[i], windows[4 * i], windows[4 * i + 1], windows[4 * i + 2], windows[4 * i + 3], 0};
+  size_t bytes = 0;                                                    // the host builder's answer to this very table, first
+  rc = dh::crop_program_bytes(jobs_host.data(), n, (int)f->px.size(), OH, OW, &bytes);
+  if (rc != DH_OK) return rc;
+  rc = host_staging(pl);
+  if (rc != DH_OK) return rc;
+  rc = crop_program_room(pl, f, 1, OH, OW);
+  if (rc != DH_OK) return rc;
+  rc = grow(&pl->crop_jobs, &pl->crop_jobs_n, (size_t)pl->n, sizeof(dh_crop_job));
+  if (rc != DH_OK) return rc;
+  // one allocation for a full batch: float64 boxes | int32 boxes | status
+  const size_t N = (size_t)pl->n;
+  rc = grow(&pl->boxes_buf, &pl->boxes_bytes, 52 * N, 1);
+  if (rc != DH_OK) return rc;
+  double* boxf = reinterpret_cast<double*>(pl->boxes_buf);
+  int32_t* box = reinterpret_cast<int32_t*>(pl->boxes_buf + 32 * N);
+  int32_t* status = reinterpret_cast<int32_t*>(pl->boxes_buf + 48 * N);
+  hipStream_t s = pl->stream;
+  if (hipMemcpyAsync(pl->crop_jobs, jobs_host.data(), (size_t)n * sizeof(dh_crop_job), hipMemcpyHostToDevice, s) != hipSuccess)
+    return DH_ELAUNCH;
+  const In& in = pl->ins[0];
+  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
+  const float* view = reinterpret_cast<const float*>(pl->arena + o.off);
+  rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), pl->crop_jobs, n, OH, OW, pl->crop_prog, pl->crop_prog_bytes, nullptr, s);
+  if (rc == DH_OK) rc = dh_crop_resize_u8(pl->crop_prog, n, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, s);
+  if (rc == DH_OK) {
+    pl->out_ptr.assign(pl->outs.size(), nullptr);                      // no output is packed: the poses are read in the arena
+    rc = dh_forward(pl, inputs, n, pl->out_ptr.data(), s);
+  }
+  // the boxes from the poses where the forward left them: same stream, behind the plan's join -- no event
+  if (rc == DH_OK)
+    rc = dh_pose_boxes_f64(view, (int64_t)o.npix * o.ld, (int64_t)o.npix * o.ld, o.ld, 1, J, o.C - 2, pl->crop_jobs, 1, n, relsize, box,
+                           boxf, status, s);
+  if (rc != DH_OK) {
+    hipStreamSynchronize(s);                                           // nothing of this call stays in flight behind a refusal
+    return rc;
+  }
+  bool ok = hipMemcpyAsync(boxes_out, box, 16 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess;
+  ok = ok && hipMemcpyAsync(boxes_f64_out, boxf, 32 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess;
+  ok = ok && hipMemcpyAsync(status_out, status, 4 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess;
   if (hipStreamSynchronize(s) != hipSuccess || !ok) return DH_ELAUNCH;
   return DH_OK;
 }

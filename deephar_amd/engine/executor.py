@@ -1114,6 +1114,104 @@ class Executor:
                for t in range(num_iter)]
         return raw, jobs_host, status_host
 
+    def run_frame_boxes(self, store, index, windows, out_hw, outidx, relsize, bs, u8_norm):
+        with self._lock:          # one thread at a time on the shared stream (engine/executor.py: stream_lock)
+            return self._run_frame_boxes_locked(store, index, windows, out_hw, outidx, relsize, bs, u8_norm)
+
+    def _run_frame_boxes_locked(self, store, index, windows, out_hw, outidx, relsize, bs, u8_norm):
+        """The per-frame person-box pass (evaltools.bbox.predict_frame_bboxes_frames) with the pose -> box step on the device:
+        all N items as nchunks chunks on the compute stream, ONE stream of launches without a host wait in between and no
+        packed-output transfer -- 52 bytes per item leave the device, once, at the end.
+          once     : the job table int32 [N * per_item, 6] goes to the device (index [N]: per_item = 1; index [N, T] of a clip
+                     model: per_item = T, the item's window broadcast over its frames).
+          per chunk: dh_crop_program_build_dev from the resident slice of the job table (per-job status kept),
+                     dh_crop_resize_u8 into the plan's uint8 input, the forward, then dh_pose_boxes_f64 reads output `outidx`
+                     where it lies in the arena (confidence channel D - 2) and the item's window at jobs[i * per_item], and
+                     writes the chunk's rows of the box and status tables.  The forward joins its side streams before it
+                     returns, so output `outidx` is complete on this stream: no event, as in run_refine.
+          at the end: one copy each of the int32 boxes, the float64 boxes, the statuses and the builder's statuses into pinned
+                     memory, behind everything on the stream, and ONE drain.
+        One program buffer serves every chunk (its only reader is the crop launch right behind the builder).
+        Returns (boxes int32 [N, 4], boxes float64 [N, 4], status int32 [N], the builder's status int32 [N, per_item]).  A
+        refused job leaves its input frame as the previous chunk left it; the caller raises for it."""
+        torch = _torch()
+        lib = _lib.load()
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        if len(self.plan.inputs) != 1:
+            raise ValueError('the device box pass feeds a single image input, the plan has %d inputs' % len(self.plan.inputs))
+        in_shape = tuple(self.plan.inputs[0].shape)
+        if u8_norm is None or len(in_shape) not in (3, 4) or in_shape[-3:] != (OH, OW, 3):
+            raise ValueError('the device box pass feeds a uint8 image input [(T,) %d, %d, 3], not %s' % (OH, OW, in_shape))
+        per_item = 1 if len(in_shape) == 3 else int(in_shape[0])
+        nout = len(self.plan.outputs)
+        if not -nout <= outidx < nout:
+            raise ValueError('output %d of %d' % (outidx, nout))
+        vout = self.plan.outputs[outidx]
+        if len(vout.shape) != len(in_shape) - 1 or vout.shape[-1] < 2 or (per_item > 1 and vout.shape[0] != per_item):
+            raise ValueError('output %d %s is no pose output [(T,) J, D >= 2]' % (outidx, tuple(vout.shape)))
+        index = np.ascontiguousarray(index, np.int32)
+        windows = np.ascontiguousarray(windows, np.int32)
+        total = index.shape[0]
+        if total < 1 or index.shape != ((total,) if per_item == 1 else (total, per_item)) or windows.shape != (total, 4):
+            raise ValueError('index %s and windows %s do not describe items of %d frame(s)' % (index.shape, windows.shape, per_item))
+        if index.min() < 0 or index.max() >= len(store):
+            raise ValueError('frame index outside the %d stored frames' % len(store))
+        table = np.zeros((total, per_item, 6), np.int32)
+        table[:, :, 0] = index.reshape(total, per_item)
+        table[:, :, 1:5] = windows[:, None, :]
+        bs = int(min(bs, total))
+        J, D = int(vout.shape[-2]), int(vout.shape[-1])
+        with torch.cuda.device(self.device):
+            if self.bound:
+                self.sync_weights()
+            with torch.cuda.stream(self.stream):
+                bp = self.bind(bs, u8_norm=u8_norm)
+            if self._wstamp is None:
+                self._wstamp = self._weight_stamp()
+            nbytes = C.c_size_t(0)
+            rc = lib.dh_crop_program_max_bytes(bs * per_item, len(store), OH, OW, C.byref(nbytes))
+            if rc == -2:
+                raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % (bs * per_item))
+            _lib.check(rc, 'dh_crop_program_max_bytes')
+            io = self._io(bp, 0, staged=False)                      # (no output slots: nothing is packed out)
+            if io.get('boxes_prog') is None or io['boxes_prog'].numel() < nbytes.value:
+                io['boxes_prog'] = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            prog = io['boxes_prog']
+            if io.get('boxes_host') is None or io['boxes_host'][0].shape[0] < total:     # pinned result tables, grown only
+                io['boxes_host'] = [torch.empty(shape, dtype=dt, pin_memory=True) for shape, dt in
+                                    (((total, 4), torch.int32), ((total, 4), torch.float64), ((total,), torch.int32),
+                                     ((total, per_item), torch.int32))]
+            host = [h[:total] for h in io['boxes_host']]
+            srcs_dev = store.srcs_dev
+            pose = bp.tensor(vout)                                  # [bs, (T,) J, D] where the forward leaves it
+            item_stride = pose.stride(0)
+            frame_stride = pose.stride(1) if per_item > 1 else item_stride
+            dst = bp.u8[id(self.plan.inputs[0].buf)][0]
+            try:
+                with torch.cuda.stream(self.stream):
+                    jobs = torch.from_numpy(table).to(self.device, non_blocking=True)
+                    boxes = torch.empty((total, 4), dtype=torch.int32, device=self.device)
+                    boxes_f = torch.empty((total, 4), dtype=torch.float64, device=self.device)
+                    status = torch.empty((total,), dtype=torch.int32, device=self.device)
+                    built = torch.zeros((total, per_item), dtype=torch.int32, device=self.device)
+                    for start in range(0, total, bs):
+                        m = min(bs, total - start)
+                        _lib.check(lib.dh_crop_program_build_dev(
+                            srcs_dev.data_ptr(), len(store), jobs[start].data_ptr(), m * per_item, OH, OW, prog.data_ptr(),
+                            prog.numel(), built[start].data_ptr(), self.stream_ptr), 'dh_crop_program_build_dev')
+                        _lib.check(lib.dh_crop_resize_u8(prog.data_ptr(), m * per_item, OH, OW, dst.data_ptr(), OH * OW * 3,
+                                                         self.stream_ptr), 'dh_crop_resize_u8')
+                        self.forward(bp)
+                        _lib.check(lib.dh_pose_boxes_f64(
+                            pose.data_ptr(), item_stride, frame_stride, pose.stride(-2), per_item, J, D - 2,
+                            jobs[start].data_ptr(), per_item, m, float(relsize), boxes[start].data_ptr(),
+                            boxes_f[start].data_ptr(), status[start:].data_ptr(), self.stream_ptr), 'dh_pose_boxes_f64')
+                    for h, d in zip(host, (boxes, boxes_f, status, built)):      # behind everything on the stream
+                        h.copy_(d, non_blocking=True)
+            finally:
+                self.stream.synchronize()                           # the one drain (and nothing in flight behind an exception)
+        return tuple(h.numpy().copy() for h in host)
+
     def run_device(self, tensors, n=None, inputs_copied=None):
         with self._lock:         # one thread at a time on the shared stream (engine/executor.py: stream_lock)
             return self._run_device_locked(tensors, n, inputs_copied)

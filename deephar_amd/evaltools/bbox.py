@@ -96,6 +96,48 @@ def get_bbox_from_poses(poses, afmat, scale=1.5):
     return np.array([min(c[0], c[2]), min(c[1], c[3]), max(c[0], c[2]), max(c[1], c[3])])
 
 
+def predict_frame_bboxes_frames(model, frames, index, windows, keys, scale=1.5, batch_size=32, loop='host', outidx=-1):
+    """predict_frame_bboxes over FULL frames, batched: item i is cropped on the GPU out of frame index[i] (an image model) or
+    frames index[i, :] (a clip model) with the unflipped integer window windows[i] (frontend.crop_box), and its box is keyed
+    keys[i].  `frames`: uint8 [H, W, 3] images or a frontend.FrameStore; `outidx`: the pose output the box is taken from.
+    Returns the {key: [x0, y0, x1, y1]} dictionary of predict_frame_bboxes.
+    loop='host' (the default): frontend.predict_from_frames at `batch_size`, then get_bbox_from_poses per sample on the host
+    with the returned afmat -- today's arithmetic, batched.
+    loop='device': frontend.frame_boxes_from_frames -- the pose -> box step is one small launch behind every forward
+    (dh_pose_boxes_f64) and only the boxes leave the device.  The same integer boxes unless a corner lies within rounding
+    of an integer (the host goes through np.linalg.inv of the affine map, the device through the window itself).
+    A sample with a frame that keeps no joint raises get_valid_bbox's ValueError under both loops, naming the first such
+    sample; under loop='device' after the run has drained, and a NaN joint or a corner outside int32 raises ValueError naming
+    sample and status instead of converting an undefined value."""
+    from .. import frontend
+    if loop not in ('host', 'device'):
+        raise ValueError("loop must be 'host' or 'device', got %r" % (loop,))
+    index = np.asarray(index, np.int64)
+    windows = np.asarray(windows)
+    keys = list(keys)
+    if len(keys) != len(index) or len(windows) != len(index):
+        raise ValueError('%d keys and %d windows for %d samples' % (len(keys), len(windows), len(index)))
+    if loop == 'device':
+        boxes, _, status = frontend.frame_boxes_from_frames(model, frames, index, windows, outidx=outidx, scale=scale,
+                                                            batch_size=batch_size)
+        for i in np.flatnonzero(status == 1)[:1]:
+            raise ValueError('get_valid_bbox: all points are invalid! (sample %d, key %r)' % (i, keys[i]))
+        for i in np.flatnonzero(status != 0)[:1]:
+            raise ValueError('no box for sample %d, key %r: status %d (2: a NaN joint, 3: a corner outside int32, 4: the window)'
+                             % (i, keys[i], status[i]))
+        return {k: b.tolist() for k, b in zip(keys, boxes)}
+    res = frontend.predict_from_frames(model, frames, index, windows, batch_size=batch_size)
+    pred, A = res[:-1][outidx], res[-1]
+    boxes = {}
+    for i, k in enumerate(keys):
+        try:
+            b = get_bbox_from_poses(pred[i:i + 1], A[i] if A.ndim == 3 else A[i, 0], scale=scale)
+        except ValueError as e:
+            raise ValueError('%s (sample %d, key %r)' % (e, i, k))
+        boxes[k] = b.astype(int).tolist()
+    return boxes
+
+
 def predict_frame_bboxes(model, ds, mode, scale=1.5, key=None):
     """The loop of exp/pennaction/predict_bboxes.py:53-68: one forward per sample, box from the predicted pose,
     integer box keyed '<seq_idx>.<frame>' (or key(data, i))."""

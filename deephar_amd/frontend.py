@@ -10,6 +10,8 @@ it over; program='device' stages only the chunk's 24-byte jobs and builds the pr
 the same bytes), in front of the crop launch on the compute stream.
 refine_from_frames runs the whole box-refinement loop with the boxes resident on the device (dh_refine_boxes_f64 behind every
 forward, csrc/refine_index.h): the caller the device builder was made for.
+frame_boxes_from_frames is the per-frame person-box pass: the pose -> box step is one launch behind every forward
+(dh_pose_boxes_f64, csrc/posebox_index.h) and only the boxes leave the device.
 
 Scope: the loaders' test-mode geometry -- angle 0, integer window, bilinear, optional mirror, 3 channels, uint8.  Box and
 matrix bookkeeping stays on the host in float64 (crop_box, crop_afmat), composed like deephar/utils/transform.py does.
@@ -186,6 +188,49 @@ def refine_from_frames(model, frames, index, bbox0, outidx, num_iter=2, winsize_
     for pos in np.ndindex(num_iter, total):
         afmat[pos] = crop_afmat(windows[pos], (OW, OH), False)
     return raws, windows, afmat
+
+
+def frame_boxes_from_frames(model, frames, index, windows, outidx=-1, scale=1.5, batch_size=32):
+    """The per-frame person-box pass with the pose -> box step on the GPU (Executor.run_frame_boxes): every chunk is cropped
+    out of the resident frames, predicted, and its poses are turned into boxes by dh_pose_boxes_f64 where the forward left them
+    (csrc/posebox_index.h restates evaltools.bbox.get_bbox_from_poses); no model output is copied to the host.
+    index [N] (image model) or [N, T] (clip model); windows: integer (x0, y0, x1, y1) per item as crop_box makes them, [N, 4],
+    cropped unflipped and, for a clip model, broadcast over the item's frames.
+    Returns (boxes int64 [N, 4] -- get_bbox_from_poses(...).astype(int); boxes float64 [N, 4]; status int32 [N]: 0 ok, 1 a frame
+    keeps no joint, 2 a kept joint is NaN, 3 a corner does not fit int32, 4 never here).  ValueError, after the drain, for the
+    first window the program builder refused: the errors CropFeed raises on the host for the same window."""
+    if len(model.inputs) != 1:
+        raise ValueError('frame_boxes_from_frames needs a model with a single image input, %s has %d inputs' %
+                         (model.name, len(model.inputs)))
+    shape = tuple(model.inputs[0].shape)
+    if len(shape) not in (3, 4) or shape[-1] != 3:
+        raise ValueError('frame_boxes_from_frames needs an image input [(T,) H, W, 3], the model takes %s' % (shape,))
+    index = np.asarray(index, np.int64)
+    windows = np.asarray(windows)
+    if windows.dtype.kind not in 'iu':
+        raise ValueError('windows must be integer windows (frontend.crop_box)')
+    if index.ndim != len(shape) - 2 or (len(shape) == 4 and index.shape[1] != shape[0]):
+        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, shape))
+    total = index.shape[0]
+    if windows.shape != (total, 4):
+        raise ValueError('windows %s do not give one window for each of %d items' % (windows.shape, total))
+    if total == 0:
+        return np.zeros((0, 4), np.int64), np.zeros((0, 4)), np.zeros((0,), np.int32)
+    if np.abs(windows).max() > 0x7fffffff:
+        raise ValueError('a window corner does not fit int32')
+    OH, OW = shape[-3], shape[-2]
+    ex = model.executor
+    store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
+    bs = int(min(batch_size or total, total))
+    boxes, boxes_f64, status, built = ex.run_frame_boxes(store, index, windows, (OH, OW), outidx, scale, bs, model.channel_power)
+    bad = np.argwhere(built != 0)
+    if len(bad):
+        i = int(bad[0][0])
+        if built[tuple(bad[0])] == -2:
+            raise ValueError('a crop window is more than 16 times its output on one axis (or the output row does not fit LDS): '
+                             'sample %d, window %s' % (i, windows[i].tolist()))
+        raise ValueError('empty crop box: sample %d, window %s' % (i, windows[i].tolist()))
+    return boxes.astype(np.int64), boxes_f64, status
 
 
 def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32, program='host'):

@@ -259,6 +259,48 @@ def refine_boxes(poses, jobs, boxes, winsize_scale=1.5, momentum=0.8, out_boxes=
     return nb, nj
 
 
+def pose_boxes(poses, windows, scale=1.5, conf_channel=None):
+    """One person box per item from predicted poses on the GPU (dh_pose_boxes_f64), on torch's current stream: the device form
+    of evaltools.bbox.get_bbox_from_poses.  poses: float32 CUDA [N, J, D >= 2] or [N, F, J, D] (an item of F frames) in
+    crop-normalised coordinates, any item, frame and joint strides with a unit channel stride (a view of a plan's output is
+    read where it lies); windows: the unflipped integer windows (x0, y0, x1, y1) the items were cropped with, [N, 4] (an int32
+    CUDA tensor, or anything np.asarray takes).  conf_channel: None -- D - 2, the reference's poses[..., -2:-1].
+    Returns (boxes int32 [N, 4], boxes float64 [N, 4], status int32 [N]) on the device; a non-zero status (1 a frame keeps no
+    joint, 2 a kept joint is NaN, 3 a corner does not fit int32, 4 an empty window) leaves its boxes zero."""
+    torch = _t()
+    if not (poses.is_cuda and poses.dtype == torch.float32 and poses.dim() in (3, 4) and poses.shape[-1] >= 2 and
+            poses.stride(-1) == 1):
+        raise ValueError('poses must be a float32 CUDA tensor [N, (F,) J, D >= 2] with a unit channel stride')
+    n, J, D = poses.shape[0], poses.shape[-2], poses.shape[-1]
+    F = poses.shape[1] if poses.dim() == 4 else 1
+    cc = D - 2 if conf_channel is None else int(conf_channel)
+    if not 0 <= cc < D:
+        raise ValueError('conf_channel %d outside the %d channels' % (cc, D))
+    if not torch.is_tensor(windows):
+        windows = torch.from_numpy(np.ascontiguousarray(windows, np.int32)).to(poses.device)
+    if not (windows.is_cuda and windows.dtype == torch.int32 and tuple(windows.shape) == (n, 4)):
+        raise ValueError('windows must be int32 [%d, 4] (x0, y0, x1, y1)' % n)
+    jobs = torch.zeros((n, 6), dtype=torch.int32, device=poses.device)
+    jobs[:, 1:5] = windows
+    boxes = torch.empty((n, 4), dtype=torch.int32, device=poses.device)
+    boxes_f = torch.empty((n, 4), dtype=torch.float64, device=poses.device)
+    status = torch.empty((n,), dtype=torch.int32, device=poses.device)
+    ext = max(2, cc + 1)                          # (torch gives a dimension of size 1 any stride: take the extent it spans)
+    js = poses.stride(-2) if J > 1 else max(poses.stride(-2), ext)
+    fs = (J - 1) * js + ext
+    if F > 1:
+        fs = poses.stride(1)
+    its = poses.stride(0) if n > 1 else max(poses.stride(0), (F - 1) * fs + (J - 1) * js + ext)
+    if F == 1:
+        fs = its
+    rc = _lib.load().dh_pose_boxes_f64(_p(poses), its, fs, js, F, J, cc, _p(jobs), 1, n, float(scale), _p(boxes), _p(boxes_f),
+                                       _p(status), _stream())
+    if rc == -1:
+        raise ValueError('pose_boxes: bad argument (no items, no joints, or strides smaller than the extent they span)')
+    _lib.check(rc, 'dh_pose_boxes_f64')
+    return boxes, boxes_f, status
+
+
 def dwconv2d(x, dw_kernel, pre_scale=None, pre_shift=None, pre_relu=False, up_in=False):
     """Depthwise conv, stride 1, TF-SAME.  dw_kernel numpy [kh,kw,C,1].  up_in: x is at half resolution and the
     convolution runs on UpSampling2D((2, 2))(x) without writing it out (dh_dw_args.up_in)."""

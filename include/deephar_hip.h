@@ -801,6 +801,57 @@ int dh_refine_frames_host(dh_plan* plan, const dh_frames* f, const int32_t* src,
                           int32_t* status_out /* [num_iter, n] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Person boxes from predicted poses on the device: the pose -> box step of the per-frame box pass (exp/common/generic.py:7-27
+ * and exp/{ntu,pennaction}/predict_bboxes.py in the reference, deephar_amd/evaltools/bbox.py: get_bbox_from_poses,
+ * predict_frame_bboxes_frames) as one small launch behind the forward, so that 52 bytes per item leave the device instead of
+ * the packed outputs.  The arithmetic is csrc/posebox_index.h: float32 where numpy keeps the float32 pose, double for the
+ * pixels, never fused, the same bits on the host (`_host` twin over host pointers) and on the device.
+ *   An ITEM is F poses (F = 1 for an image model, F = T for a clip model) of J joints, all predicted in ONE unflipped integer
+ *   window (x0, y0, x1, y1): job jobs[i * job_stride] of the crop job table (job_stride = frames per item).  Joint j of frame f
+ *   is float32 at poses[i * item_stride + f * frame_stride + j * joint_stride + {0, 1, conf_channel}] (strides in floats: the
+ *   launch reads a plan's output where it lies in the arena).
+ *   kept:    joint j of frame f is kept when its channel conf_channel is > 0.25 as a float32 comparison (the Python side
+ *            passes D - 2, the reference's poses[..., -2:-1]); a NaN confidence keeps nothing.
+ *   span:    per frame, in float32, over the kept joints: cx = (xmin + xmax) / 2, w = relsize (xmax - xmin) (cy, h likewise;
+ *            relsize is the double rounded once to float32), s = max(w, h); corners cx - s/2, cy - s/2, cx + s/2, cy + s/2.
+ *   union:   the exact float min of the first two and max of the last two corners over the item's frames: (u0, v0, u1, v1).
+ *   pixels:  X = x0 + (double)u (x1 - x0), Y = y0 + (double)v (y1 - y0) for both corners, each product and each sum one IEEE
+ *            double operation; the two corners ordered by min / max; boxes_f64_out[4 i ..] holds them, boxes_out[4 i ..] each
+ *            truncated toward zero (numpy's astype(int)).
+ *   status_out[i]: 0 ok; 1 a frame of the item keeps no joint (the reference raises ValueError('get_valid_bbox: all points
+ *            are invalid!')); 2 a kept joint has a NaN coordinate; 3 a corner is not finite or of magnitude >= 2^31; 4 the window
+ *            is empty or flipped.  When several hold: 1, else 2, else 4, else 3.  A non-zero status writes both boxes as four
+ *            zeros; no NaN is stored and no unrepresentable double is converted.
+ *            One wavefront per item, lanes over the joints, cross-lane min / max per frame (exact: no order dependence), lane 0
+ *            does the doubles.  No atomics; nothing allocates, nothing synchronises.
+ *   DH_EINVAL: NULL (or misaligned device) pointers; n < 1, F < 1, J < 1; conf_channel < 0; job_stride < 1; with e = max(2,
+ *            conf_channel + 1) the floats a joint spans: joint_stride < e, frame_stride < (J - 1) joint_stride + e, item_stride
+ *            < (F - 1) frame_stride + (J - 1) joint_stride + e; any stride above 2^40; (n - 1) item_stride or (n - 1) job_stride
+ *            above 2^58.
+ *   frame_boxes_host: the pass of ONE batch (n <= dh_plan_batch, single-image uint8 plans) from a C host: src (frame indices
+ *            into `f`) and windows (int32 [n, 4]) become the job table, uploaded once; dh_crop_program_build_dev,
+ *            dh_crop_resize_u8 into the plan's input, the forward (no output is packed), dh_pose_boxes_f64 on output `outidx`
+ *            in the arena with conf_channel = D - 2, and three small copies back, all on the plan's internal stream with ONE
+ *            synchronisation.  A window the host program builder refuses (empty, a frame index outside `f`, beyond the 16x scale
+ *            cap) is refused here, with its code, before anything is enqueued.
+ *   frame_boxes_shape: the refusals of frame_boxes_host on their own, GPU-free: more than one input, a float input, a clip
+ *            plan (input_items != OH * OW * 3), n outside [1, batch], outidx outside [0, num_outputs), an output of fewer than
+ *            two channels (out_channels: dh_plan_output_channels; out_items: dh_plan_output_items).  Answers J.
+ * ------------------------------------------------------------------------------------------------- */
+int dh_pose_boxes_f64(const float* poses, int64_t item_stride, int64_t frame_stride, int64_t joint_stride, int F, int J,
+                      int conf_channel, const dh_crop_job* jobs, int64_t job_stride, int n, double relsize,
+                      int32_t* boxes_out /* [n, 4] */, double* boxes_f64_out /* [n, 4] */, int32_t* status_out /* [n] */,
+                      void* stream);
+int dh_pose_boxes_host(const float* poses, int64_t item_stride, int64_t frame_stride, int64_t joint_stride, int F, int J,
+                       int conf_channel, const dh_crop_job* jobs, int64_t job_stride, int n, double relsize, int32_t* boxes_out,
+                       double* boxes_f64_out, int32_t* status_out);
+int dh_frame_boxes_shape(int num_inputs, int input_is_u8, int64_t input_items, int batch, int n, int OH, int OW, int num_outputs,
+                         int outidx, int64_t out_items, int out_channels, int* J);
+int dh_frame_boxes_host(dh_plan* plan, const dh_frames* f, const int32_t* src, const int32_t* windows /* [n, 4] */, int n, int OH,
+                        int OW, int outidx, double relsize, int32_t* boxes_out /* [n, 4] */, double* boxes_f64_out /* [n, 4] */,
+                        int32_t* status_out /* [n] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Stream-ordered runtime helpers (no torch types): graphs for launch-bound replay, events for timing.
  * ------------------------------------------------------------------------------------------------- */
 int dh_graph_begin_capture(void* stream);
