@@ -377,12 +377,39 @@ int grow(T** buf, size_t* have, size_t need, size_t elem) {
   return DH_OK;
 }
 
-// the plan's device crop program, large enough for a FULL batch over the frames of `f`: one allocation per plan
-int crop_program_room(dh_plan* pl, const dh_frames* f, int per_item, int OH, int OW) {
+// the ONE build -> crop -> forward sequence of dh_forward_frames, dh_refine_frames_host and dh_frame_boxes_host, on `stream`:
+// room for the plan's device crop program (one allocation per plan, large enough for a FULL batch of `per_item` frames over the
+// frames of `f`), dh_crop_program_build_dev from `njobs` resident jobs (per-job status to `status` unless null), ONE crop
+// launch straight into the plan's uint8 input, then the forward of m items with that input in place.
+int crop_forward(dh_plan* pl, const dh_frames* f, const dh_crop_job* jobs_dev, int njobs, int per_item, int m, int OH, int OW,
+                 int32_t* status, float* const* outputs_dev, void* stream) {
   size_t need = 0;
-  const int rc = dh_crop_program_max_bytes(pl->n * per_item, (int)f->px.size(), OH, OW, &need);
+  int rc = dh_crop_program_max_bytes(pl->n * per_item, (int)f->px.size(), OH, OW, &need);
+  if (rc == DH_OK) rc = grow(&pl->crop_prog, &pl->crop_prog_bytes, need, 1);
   if (rc != DH_OK) return rc;
-  return grow(&pl->crop_prog, &pl->crop_prog_bytes, need, 1);
+  const In& in = pl->ins[0];
+  rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), jobs_dev, njobs, OH, OW, pl->crop_prog, pl->crop_prog_bytes, status,
+                                 stream);
+  if (rc != DH_OK) return rc;
+  rc = dh_crop_resize_u8(pl->crop_prog, njobs, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, stream);
+  if (rc != DH_OK) return rc;
+  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
+  return dh_forward(pl, inputs, m, outputs_dev, stream);
+}
+
+// the plan's device job table, large enough for a FULL batch of `per_item` frames, with `njobs` jobs of the host on their way
+int upload_jobs(dh_plan* pl, const dh_crop_job* jobs_host, int njobs, int per_item) {
+  const int rc = grow(&pl->crop_jobs, &pl->crop_jobs_n, (size_t)pl->n * (size_t)per_item, sizeof(dh_crop_job));
+  if (rc != DH_OK) return rc;
+  return hipMemcpyAsync(pl->crop_jobs, jobs_host, (size_t)njobs * sizeof(dh_crop_job), hipMemcpyHostToDevice, pl->stream) == hipSuccess
+             ? DH_OK : DH_ELAUNCH;
+}
+
+// how a *_host entry point ends: behind a refusal nothing of the call stays in flight; else the wait for its copies (`copies_ok`)
+int finish(dh_plan* pl, int rc, bool copies_ok) {
+  const bool synced = hipStreamSynchronize(pl->stream) == hipSuccess;
+  if (rc != DH_OK) return rc;
+  return synced && copies_ok ? DH_OK : DH_ELAUNCH;
 }
 
 // dh_forward_frames_shape of this plan: the items `njobs` crops of OH x OW x 3 bytes fill and the frames per item, or DH_EINVAL
@@ -467,16 +494,7 @@ int dh_forward_frames(dh_plan* pl, const dh_frames* f, const dh_crop_job* jobs_d
   int m = 0, per_item = 0;
   int rc = frames_shape(pl, njobs, OH, OW, &m, &per_item);
   if (rc != DH_OK) return rc;
-  rc = crop_program_room(pl, f, per_item, OH, OW);
-  if (rc != DH_OK) return rc;
-  const In& in = pl->ins[0];
-  rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), jobs_dev, njobs, OH, OW, pl->crop_prog, pl->crop_prog_bytes, nullptr,
-                                 stream);
-  if (rc != DH_OK) return rc;
-  rc = dh_crop_resize_u8(pl->crop_prog, njobs, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, stream);
-  if (rc != DH_OK) return rc;
-  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
-  return dh_forward(pl, inputs, m, outputs_dev, stream);
+  return crop_forward(pl, f, jobs_dev, njobs, per_item, m, OH, OW, nullptr, outputs_dev, stream);
 }
 
 int dh_forward_frames_host(dh_plan* pl, const dh_frames* f, const dh_crop_job* jobs_host, int njobs, int OH, int OW,
@@ -490,13 +508,10 @@ int dh_forward_frames_host(dh_plan* pl, const dh_frames* f, const dh_crop_job* j
   if (rc != DH_OK) return rc;
   rc = host_staging(pl);
   if (rc != DH_OK) return rc;
-  const size_t full = (size_t)pl->n * (size_t)per_item;
-  rc = grow(&pl->crop_jobs, &pl->crop_jobs_n, full, sizeof(dh_crop_job));
+  rc = upload_jobs(pl, jobs_host, njobs, per_item);
   if (rc != DH_OK) return rc;
-  if (hipMemcpyAsync(pl->crop_jobs, jobs_host, (size_t)njobs * sizeof(dh_crop_job), hipMemcpyHostToDevice, pl->stream) != hipSuccess)
-    return DH_ELAUNCH;
   const size_t used = place_outputs(pl, outputs_host, m);
-  rc = dh_forward_frames(pl, f, pl->crop_jobs, njobs, OH, OW, pl->out_ptr.data(), pl->stream);
+  rc = crop_forward(pl, f, pl->crop_jobs, njobs, per_item, m, OH, OW, nullptr, pl->out_ptr.data(), pl->stream);
   if (rc != DH_OK) return rc;
   return fetch_outputs(pl, outputs_host, m, used);
 }
@@ -515,8 +530,6 @@ int dh_refine_frames_host(dh_plan* pl, const dh_frames* f, const int32_t* src, c
   if (rc != DH_OK) return rc;
   if ((int64_t)num_iter * pl->n > 0x7fffffff / 64) return DH_EINVAL;
   rc = host_staging(pl);
-  if (rc != DH_OK) return rc;
-  rc = crop_program_room(pl, f, 1, OH, OW);
   if (rc != DH_OK) return rc;
   // one allocation for a full batch: boxes | jobs of every iteration | status of every iteration | src | poses of every iteration
   const size_t N = (size_t)pl->n, T = (size_t)num_iter;
@@ -538,28 +551,17 @@ int dh_refine_frames_host(dh_plan* pl, const dh_frames* f, const int32_t* src, c
     return DH_ELAUNCH;
   rc = dh_jobs_from_boxes_f64(boxes, src_dev, n, jobs, s);
   if (rc != DH_OK) return rc;
-  const In& in = pl->ins[0];
-  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
   const float* view = reinterpret_cast<const float*>(pl->arena + o.off);
-  for (int t = 0; t < num_iter; ++t) {
+  for (int t = 0; rc == DH_OK && t < num_iter; ++t) {
     dh_crop_job* jt = jobs + (size_t)t * (size_t)n;
-    rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), jt, n, OH, OW, pl->crop_prog, pl->crop_prog_bytes,
-                                   status + (size_t)t * (size_t)n, s);
-    if (rc == DH_OK) rc = dh_crop_resize_u8(pl->crop_prog, n, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, s);
-    if (rc != DH_OK) break;
     pl->out_ptr.assign(pl->outs.size(), nullptr);                      // only the pose output is packed
     pl->out_ptr[(size_t)outidx] = poses + (size_t)t * pose_floats;
-    rc = dh_forward(pl, inputs, n, pl->out_ptr.data(), s);
-    if (rc != DH_OK) break;
+    rc = crop_forward(pl, f, jt, n, 1, n, OH, OW, status + (size_t)t * (size_t)n, pl->out_ptr.data(), s);
     // the next window from the poses where the forward left them: same stream, behind the plan's join -- no event
-    if (t + 1 < num_iter)
+    if (rc == DH_OK && t + 1 < num_iter)
       rc = dh_refine_boxes_f64(view, (int64_t)o.npix * o.ld, o.ld, J, jt, boxes, n, winsize_scale, momentum, boxes, jt + n, s);
-    if (rc != DH_OK) break;
   }
-  if (rc != DH_OK) {
-    hipStreamSynchronize(s);                                           // nothing of this call stays in flight behind a refusal
-    return rc;
-  }
+  if (rc != DH_OK) return finish(pl, rc, false);
   const size_t item_floats = o.npix * (size_t)o.C * (size_t)n;
   bool ok = true;
   for (int t = 0; ok && t < num_iter; ++t)
@@ -567,8 +569,7 @@ int dh_refine_frames_host(dh_plan* pl, const dh_frames* f, const int32_t* src, c
          hipSuccess;
   ok = ok && hipMemcpyAsync(jobs_out, jobs, sizeof(dh_crop_job) * (size_t)n * T, hipMemcpyDeviceToHost, s) == hipSuccess;
   ok = ok && hipMemcpyAsync(status_out, status, 4 * (size_t)n * T, hipMemcpyDeviceToHost, s) == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) return DH_ELAUNCH;
-  return DH_OK;
+  return finish(pl, DH_OK, ok);
 }
 
 // ---- the per-frame person-box pass of one batch: only the boxes and their status leave the device ---------------------------------
@@ -591,10 +592,6 @@ int dh_frame_boxes_host(dh_plan* pl, const dh_frames* f, const int32_t* src, con
   if (rc != DH_OK) return rc;
   rc = host_staging(pl);
   if (rc != DH_OK) return rc;
-  rc = crop_program_room(pl, f, 1, OH, OW);
-  if (rc != DH_OK) return rc;
-  rc = grow(&pl->crop_jobs, &pl->crop_jobs_n, (size_t)pl->n, sizeof(dh_crop_job));
-  if (rc != DH_OK) return rc;
   // one allocation for a full batch: float64 boxes | int32 boxes | status
   const size_t N = (size_t)pl->n;
   rc = grow(&pl->boxes_buf, &pl->boxes_bytes, 52 * N, 1);
@@ -603,30 +600,20 @@ int dh_frame_boxes_host(dh_plan* pl, const dh_frames* f, const int32_t* src, con
   int32_t* box = reinterpret_cast<int32_t*>(pl->boxes_buf + 32 * N);
   int32_t* status = reinterpret_cast<int32_t*>(pl->boxes_buf + 48 * N);
   hipStream_t s = pl->stream;
-  if (hipMemcpyAsync(pl->crop_jobs, jobs_host.data(), (size_t)n * sizeof(dh_crop_job), hipMemcpyHostToDevice, s) != hipSuccess)
-    return DH_ELAUNCH;
-  const In& in = pl->ins[0];
-  const float* inputs[1] = {reinterpret_cast<const float*>(in.dst)};  // written in place: dh_forward skips the input copy
+  rc = upload_jobs(pl, jobs_host.data(), n, 1);
+  if (rc != DH_OK) return rc;
   const float* view = reinterpret_cast<const float*>(pl->arena + o.off);
-  rc = dh_crop_program_build_dev(f->table, (int)f->px.size(), pl->crop_jobs, n, OH, OW, pl->crop_prog, pl->crop_prog_bytes, nullptr, s);
-  if (rc == DH_OK) rc = dh_crop_resize_u8(pl->crop_prog, n, OH, OW, reinterpret_cast<uint8_t*>(in.dst), (int64_t)OH * OW * 3, s);
-  if (rc == DH_OK) {
-    pl->out_ptr.assign(pl->outs.size(), nullptr);                      // no output is packed: the poses are read in the arena
-    rc = dh_forward(pl, inputs, n, pl->out_ptr.data(), s);
-  }
+  pl->out_ptr.assign(pl->outs.size(), nullptr);                        // no output is packed: the poses are read in the arena
+  rc = crop_forward(pl, f, pl->crop_jobs, n, 1, n, OH, OW, nullptr, pl->out_ptr.data(), s);
   // the boxes from the poses where the forward left them: same stream, behind the plan's join -- no event
   if (rc == DH_OK)
     rc = dh_pose_boxes_f64(view, (int64_t)o.npix * o.ld, (int64_t)o.npix * o.ld, o.ld, 1, J, o.C - 2, pl->crop_jobs, 1, n, relsize, box,
                            boxf, status, s);
-  if (rc != DH_OK) {
-    hipStreamSynchronize(s);                                           // nothing of this call stays in flight behind a refusal
-    return rc;
-  }
+  if (rc != DH_OK) return finish(pl, rc, false);
   bool ok = hipMemcpyAsync(boxes_out, box, 16 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess;
   ok = ok && hipMemcpyAsync(boxes_f64_out, boxf, 32 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess;
   ok = ok && hipMemcpyAsync(status_out, status, 4 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) return DH_ELAUNCH;
-  return DH_OK;
+  return finish(pl, DH_OK, ok);
 }
 
 }  // extern "C"

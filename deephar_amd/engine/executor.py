@@ -6,11 +6,12 @@ torch compute and no CPU fallback.  The launch sequence of a bound plan is captu
 (dh_graph_*), so steady-state `predict` costs one graph launch per batch instead of ~300 kernel launches.
 """
 import ctypes as C
+import itertools
 import os
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, frontend
 from . import binding, packing
 from .binding import grid_x, grid_depth      # noqa: F401  (their home is the binder; functional.py and the tests look here)
 
@@ -159,6 +160,18 @@ class _InputStep:
 from .planner import split_k_rule      # noqa: E402  (the rule is stated once, next to the planner rule that uses it)
 
 
+def value_view(flat, v, n):
+    """torch view [n, *shape] of a Value (strided when it lives inside a wider buffer) in `flat`: the arena of a plan bound at n,
+    or a copy of its head (OutputRing: the packed output region arena[0 : out_items * n])."""
+    shape = (n,) + v.shape
+    strides = [1] * len(shape)
+    if len(shape) >= 2:
+        strides[-2] = v.ld
+        for i in range(len(shape) - 3, -1, -1):
+            strides[i] = strides[i + 1] * shape[i + 1]
+    return _torch().as_strided(flat, shape, strides, v.buf.offset * n + v.coff)
+
+
 class BoundPlan:
     """A Plan with concrete device pointers for batch size n."""
 
@@ -199,6 +212,17 @@ class BoundPlan:
         self.noop_calls = set()   # indices of `calls` whose work moved into an earlier, grouped launch
         self.paired = []          # (index of the paired launch, index of the launch it absorbed): _pair_skinny_convs
         self.absorbed = {}        # index of a grouped / paired launch -> the Step whose work it also does
+        # what the Executor's chunk loops keep per bound plan, across calls: all of it only grows (pinned allocation costs
+        # milliseconds, and a warm second call must allocate nothing)
+        self.ring = OutputRing(plan, n, self.arena)   # pinned slots for the packed outputs
+        self.h2d = []             # per slot: the event that orders the slot's upload (copy stream) before the compute stream
+        self.array_slots = []     # ArrayFeed: per slot (pinned staging per input, their device twins)
+        self.byte_slots = []      # frontend.CropFeed: per slot (pinned uint8, device uint8): a crop program or a job table
+        # the ONE device crop program of this plan (Executor.crop_room / crop_step).  One buffer is enough for every slot and
+        # every loop: its only reader is the crop launch right behind the builder on the compute stream, and the next builder is
+        # enqueued on that stream behind the forward's join -- what run_refine, run_frame_boxes and plan.hip (pl->crop_prog) rely on
+        self.crop_prog = None
+        self.boxes_host = None    # run_frame_boxes: the pinned result tables
 
     # ---- views -------------------------------------------------------------------------------------------
     def ptr(self, v):
@@ -206,15 +230,11 @@ class BoundPlan:
 
     def tensor(self, v):
         """torch view [n, *shape] of a Value (strided when it lives inside a wider buffer)."""
-        torch = _torch()
-        shape = (self.n,) + v.shape
-        strides = [1] * len(shape)
-        strides[-1] = 1
-        if len(shape) >= 2:
-            strides[-2] = v.ld
-            for i in range(len(shape) - 3, -1, -1):
-                strides[i] = strides[i + 1] * shape[i + 1]
-        return torch.as_strided(self.arena, shape, strides, v.buf.offset * self.n + v.coff)
+        return value_view(self.arena, v, self.n)
+
+    def input_bytes(self):
+        """The uint8 staging tensor [n, ...] of the first input of a uint8-bound plan: what a crop launch fills."""
+        return self.u8[id(self.plan.inputs[0].buf)][0]
 
     # ---- binding: the env of engine/binding.py over the arena and the WeightStore, and the part that needs a device ----------
     def affine(self, layer):
@@ -665,6 +685,127 @@ def _staging_pool():
     return _POOL
 
 
+# ---- the chunk loops of the Executor: their arithmetic, their output ring, the host-array feed ----------------------------------
+def chunk_steps(total, bs, depth, passes=1):
+    """The chunk-steps of `passes` passes over rows 0 .. total - 1 in chunks of `bs`, on a ring of `depth` slots, pass-major:
+    yields (step, pass t, chunk ci, slot = step % depth, start = ci * bs, m = min(bs, total - start)).  GPU-free."""
+    nchunks = -(-total // bs)
+    for step in range(passes * nchunks):
+        t, ci = divmod(step, nchunks)
+        yield step, t, ci, step % depth, ci * bs, min(bs, total - ci * bs)
+
+
+def ring_depth(steps, slot_bytes=0):
+    """Slots for `steps` chunk-steps: one per step, at most DEEPHAR_PREDICT_DEPTH (8) and -- where every slot stages
+    `slot_bytes` of input in pinned memory -- at most 512 MB of staging per bound plan; never fewer than 2.  GPU-free."""
+    cap = max(2, (512 << 20) // slot_bytes) if slot_bytes else steps
+    return max(2, min(steps, int(os.environ.get('DEEPHAR_PREDICT_DEPTH', '8')), cap))
+
+
+class OutputRing:
+    """Per bound plan: slots of pinned host memory for the packed outputs of a forward (arena[0 : out_items * n]), the event
+    behind each slot's D2H and the rows pending in it.  The chunk loops submit a slot behind every forward and reclaim it --
+    the one host wait -- only when they need the slot again or drain."""
+
+    def __init__(self, plan, n, arena):
+        self.plan, self.n, self.arena = plan, n, arena
+        self.host, self.done, self.pending = [], [], []
+
+    def grow(self, depth):
+        torch = _torch()
+        while len(self.host) < depth:
+            self.host.append(torch.empty(max(self.plan.out_items * self.n, 4), dtype=torch.float32, pin_memory=True))
+            self.done.append(torch.cuda.Event())
+            self.pending.append(None)
+
+    def submit(self, slot, m, stream):
+        """Behind a forward of m rows on `stream`: ONE D2H of the packed outputs of the whole model into the slot."""
+        self.host[slot].copy_(self.arena[:self.host[slot].numel()], non_blocking=True)
+        self.done[slot].record(stream)
+        self.pending[slot] = m
+
+    def reclaim(self, slot, results, only=None):
+        """If the slot holds rows: wait for its D2H and append to `results` one fresh array per output (a list), or the
+        array of output `only` alone, sliced out of the packed region."""
+        m = self.pending[slot]
+        if m is not None:
+            self.done[slot].synchronize()
+            outs = self.plan.outputs
+            fresh = [np.array(value_view(self.host[slot], v, self.n)[:m].numpy(), dtype=np.float32, copy=True, order='C')
+                     for v in (outs if only is None else [outs[only]])]
+            results.append(fresh if only is None else fresh[0])
+            self.pending[slot] = None
+
+    def drain(self, step, depth, results, only=None):
+        """Reclaim every slot of a ring of `depth` whose next chunk-step would be `step`: the oldest pending one first."""
+        for k in range(depth):
+            self.reclaim((step + k) % depth, results, only)
+
+    def abandon(self, stream):
+        """A call that died mid-loop must not leak rows into the next one: wait for whatever is in flight, forget it."""
+        if any(p is not None for p in self.pending):
+            stream.synchronize()
+            self.pending = [None] * len(self.pending)
+
+
+class ArrayFeed:
+    """Executor.run_pipelined's feed of host arrays (equal leading dim; an array may also be a device tensor).  Per slot:
+    pinned host staging in the dtype that crosses PCIe (uint8 frames or float32 -- float64 loader arrays are cast on the HOST
+    while being copied into the pinned buffer) and its device twin.
+    A feed is driven through three calls per chunk: stage_chunk (start the host-side staging into a slot on the pool, return the
+    futures), upload (enqueue the slot's upload; the copy stream is current), fill (enqueue what fills the plan's input; the
+    compute stream is current) -- after slot_bytes (what a slot pins, for ring_depth) and open (the slots, grown only)."""
+
+    def __init__(self, plan, arrays):
+        self.plan, self.arrays, self.total = plan, arrays, arrays[0].shape[0]
+
+    def slot_bytes(self, bs, u8):
+        return sum(bs * int(np.prod(v.shape)) for v in self.plan.inputs) * (1 if u8 else 4)
+
+    def open(self, ex, bp, bs, depth):
+        torch = _torch()
+        self.bp, self.want, self.dev_src = bp, torch.uint8 if bp.u8 is not None else torch.float32, {}
+
+        def alloc(**where):
+            return [torch.empty((bp.n,) + v.shape, dtype=self.want, **where) for v in self.plan.inputs]
+        while len(bp.array_slots) < depth:
+            bp.array_slots.append((alloc(pin_memory=True), alloc(device=ex.device)))
+
+    def stage_chunk(self, pool, slot, start, m):
+        torch = _torch()
+        dev_src, futs = [], []
+        for k, (v, arr) in enumerate(zip(self.plan.inputs, self.arrays)):
+            part = arr[start:start + m]
+            if tuple(part.shape[1:]) != tuple(v.shape):
+                raise ValueError('input has shape %s, model expects [N, %s]' % (tuple(arr.shape), tuple(v.shape)))
+            src = torch.from_numpy(np.ascontiguousarray(part)) if isinstance(part, np.ndarray) else part
+            if (src.dtype == torch.uint8) != (self.want == torch.uint8):
+                raise ValueError('plan bound for %s inputs, got %s' % (self.want, src.dtype))
+            dev_src.append(src if src.is_cuda else None)
+            if not src.is_cuda:                         # host-side cast (f64 -> f32) + pin, row slices in parallel
+                dst = self.bp.array_slots[slot][0][k]
+                nsl = max(1, min(_STAGING_THREADS, src.numel() * src.element_size() >> 22, m))
+                step = -(-m // nsl)
+                for a0 in range(0, m, step):
+                    a1 = min(a0 + step, m)              # a ragged last chunk: both slices stop at m
+                    futs.append(pool.submit(dst[a0:a1].copy_, src[a0:a1]))
+        self.dev_src[slot] = dev_src                    # (until the slot's upload: a slot is staged again only behind it)
+        return futs
+
+    def upload(self, slot, m, staged, copy_stream):
+        host, dev = self.bp.array_slots[slot]
+        dev_src = self.dev_src.pop(slot)
+        if any(s is not None for s in dev_src):         # the caller's device data may still be in flight on ITS stream
+            copy_stream.wait_stream(_torch().cuda.current_stream())
+        for k, s in enumerate(dev_src):
+            dev[k][:m].copy_(host[k][:m] if s is None else s, non_blocking=True)
+
+    def fill(self, slot, m):
+        for k, v in enumerate(self.plan.inputs):
+            dst = self.bp.u8[id(v.buf)][0] if self.bp.u8 is not None else self.bp.tensor(v)
+            dst[:m].copy_(self.bp.array_slots[slot][1][k][:m], non_blocking=True)
+
+
 class Executor:
     def __init__(self, plan, device=None, use_graph=True, autotune=True, stream_role='compute'):
         torch = _torch()
@@ -788,70 +929,36 @@ class Executor:
         """arrays: list of host arrays with equal leading dim m <= n.  Returns list of np.float32 outputs."""
         return self.run_pipelined(arrays, n or arrays[0].shape[0], u8_norm=u8_norm)
 
+    # ---- the chunk loops: what they share ----------------------------------------------------------------------------
+    def _begin(self, bs, u8_norm=None):
+        """What every run_* does first (under the lock, on this device): the device weights follow the host Params if
+        anything is bound, the plan is bound at `bs` on the executor stream, the weight stamp is taken on first use."""
+        if self.bound:
+            self.sync_weights()
+        with _torch().cuda.stream(self.stream):
+            bp = self.bind(bs, u8_norm=u8_norm)
+        if self._wstamp is None:
+            self._wstamp = self._weight_stamp()
+        return bp
+
+    def crop_room(self, bp, store, njobs, OH, OW):
+        """bp.crop_prog (one per bound plan, grown only) takes the device program of `njobs` crops out of `store`."""
+        nbytes = frontend.crop_program_max_bytes(bp.lib, njobs, len(store), OH, OW)
+        if bp.crop_prog is None or bp.crop_prog.numel() < nbytes:
+            bp.crop_prog = _torch().empty(nbytes, dtype=_torch().uint8, device=self.device)
+        store.srcs_dev                    # (uploaded on first use, with a device-wide wait: here, in front of the loop)
+
+    def crop_step(self, bp, store, jobs_ptr, njobs, OH, OW, status_ptr=None):
+        """Enqueue on the compute stream: dh_crop_program_build_dev from `njobs` resident jobs into bp.crop_prog (per-job
+        status to `status_ptr` if given), then ONE dh_crop_resize_u8 launch that writes the crops straight into the plan's
+        uint8 input -- no intermediate tensor."""
+        prog, dst = bp.crop_prog, bp.input_bytes()
+        _lib.check(bp.lib.dh_crop_program_build_dev(store.srcs_dev.data_ptr(), len(store), jobs_ptr, njobs, OH, OW, prog.data_ptr(),
+                                                    prog.numel(), status_ptr, self.stream_ptr), 'dh_crop_program_build_dev')
+        _lib.check(bp.lib.dh_crop_resize_u8(prog.data_ptr(), njobs, OH, OW, dst.data_ptr(), OH * OW * 3, self.stream_ptr),
+                   'dh_crop_resize_u8')
+
     # ---- the Model.predict boundary: host arrays in, host arrays out ---------------------------------------------
-    def _io(self, bp, depth, staged=True):
-        """Per bound plan: a ring of `depth` slots of pinned host staging (inputs in the dtype that crosses PCIe: uint8
-        frames or float32 -- float64 loader arrays are cast on the HOST while being copied into the pinned buffer),
-        their device twins, one pinned buffer per slot for the packed outputs, and the events ordering the streams.
-        staged=False (the crop front end writes the plan's input itself): no input staging is allocated; the slots hold
-        the crop programs instead (_crop_slots)."""
-        io = getattr(bp, '_io', None)
-        if io is None:
-            io = bp._io = dict(host_in=[], dev_in=[], host_out=[], h2d=[], done=[], pending=[], prog_host=[], prog_dev=[])
-        torch = _torch()
-        dt = torch.uint8 if bp.u8 is not None else torch.float32
-        while staged and len(io['host_in']) < depth:
-            io['host_in'].append([torch.empty((bp.n,) + v.shape, dtype=dt, pin_memory=True) for v in self.plan.inputs])
-            io['dev_in'].append([torch.empty((bp.n,) + v.shape, dtype=dt, device=self.device) for v in self.plan.inputs])
-        while len(io['host_out']) < depth:
-            io['host_out'].append(torch.empty(max(self.plan.out_items * bp.n, 4), dtype=torch.float32, pin_memory=True))
-            io['h2d'].append(torch.cuda.Event())
-            io['done'].append(torch.cuda.Event())
-            io['pending'].append(None)
-        return io
-
-    def _crop_slots(self, io, depth, nbytes):
-        """Per slot: pinned host memory for a chunk's crop program and its device twin, at least `nbytes` each."""
-        torch = _torch()
-        for k in range(depth):
-            if k >= len(io['prog_host']):
-                io['prog_host'].append(None)
-                io['prog_dev'].append(None)
-            if io['prog_host'][k] is None or io['prog_host'][k].numel() < nbytes:
-                io['prog_host'][k] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-                io['prog_dev'][k] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-
-    def _crop_slots_device(self, io, depth, job_bytes, prog_bytes):
-        """program='device', per slot: pinned host memory for a chunk's JOB table and its device twin (`job_bytes`), and one
-        device buffer of `prog_bytes` the GPU builds the chunk's crop program in.  No pinned program."""
-        torch = _torch()
-        for key in ('jobs_host', 'jobs_dev', 'prog_built'):
-            io.setdefault(key, [])
-        for k in range(depth):
-            if k >= len(io['jobs_host']):
-                for key in ('jobs_host', 'jobs_dev', 'prog_built'):
-                    io[key].append(None)
-            if io['jobs_host'][k] is None or io['jobs_host'][k].numel() < job_bytes:
-                io['jobs_host'][k] = torch.empty(job_bytes, dtype=torch.uint8, pin_memory=True)
-                io['jobs_dev'][k] = torch.empty(job_bytes, dtype=torch.uint8, device=self.device)
-            if io['prog_built'][k] is None or io['prog_built'][k].numel() < prog_bytes:
-                io['prog_built'][k] = torch.empty(prog_bytes, dtype=torch.uint8, device=self.device)
-
-    def _host_outputs(self, bp, flat, m):
-        """Slice the packed output region (host copy of arena[0 : out_items * n]) into one fresh array per output."""
-        torch = _torch()
-        outs = []
-        for v in self.plan.outputs:
-            shape = (bp.n,) + v.shape
-            strides = [1] * len(shape)
-            if len(shape) >= 2:
-                strides[-2] = v.ld
-                for i in range(len(shape) - 3, -1, -1):
-                    strides[i] = strides[i + 1] * shape[i + 1]
-            view = torch.as_strided(flat, shape, strides, v.buf.offset * bp.n + v.coff)
-            outs.append(np.array(view[:m].numpy(), dtype=np.float32, copy=True, order='C'))
-        return outs
-
     def run_pipelined(self, arrays, bs, u8_norm=None, verbose=0, crop=None):
         with self._lock:          # one thread at a time on the shared stream (engine/executor.py: stream_lock)
             return self._run_pipelined_locked(arrays, bs, u8_norm, verbose, crop)
@@ -866,144 +973,69 @@ class Executor:
              compute: staging -> plan input (D2D), hipGraph replay, ONE D2H of the packed outputs of the whole model
                       (arena[0 : out_items * n]) into pinned memory.
            The ring of staging slots is DEEP (up to DEEPHAR_PREDICT_DEPTH = 8 chunks in flight, capped at 512 MB of
-           pinned staging per bound plan): on this stack every host-side wait that actually has to block is followed by
-           a 40-70 ms hole in the GPU's timeline, even though later chunks are already queued
+           pinned staging per bound plan: ring_depth): on this stack every host-side wait that actually has to block is
+           followed by a 40-70 ms hole in the GPU's timeline, even though later chunks are already queued
            (profiles/r02_predict_boundary.md) -- so the host enqueues ahead and waits as late as it can.
+           The three stages are a FEED's (ArrayFeed above); the loop does not know which one it drives.
            crop (frontend.CropFeed; `arrays` is None): the input is cropped out of device-resident full frames instead of
            copied in.  host: chunk i+2's crop program (source table, jobs, coefficient tables) is built into pinned memory
            on the pool; copy: the program goes to the device; compute: ONE dh_crop_resize_u8 launch writes the chunk's
            crops straight into the plan's uint8 input, then the same forward and D2H.  Same slots, same events, no host
            synchronisation between chunks.  crop.program == 'device': host: chunk i+2's JOB table (24 bytes per crop) goes
-           into pinned memory; copy: the jobs go to the device; compute: dh_crop_program_build_dev builds the program on the
-           GPU from the store's resident source table, then the same crop launch, forward and D2H.
+           into pinned memory; copy: the jobs go to the device; compute: crop_step builds the program on the GPU from the
+           store's resident source table, then the same crop launch, forward and D2H.
            Returns one np.float32 array per model output, rows in input order (keras Model.predict semantics:
            exp/common/*_tools.py; timing method of exp/pennaction/eval_speed2d.py:70-77)."""
         torch = _torch()
-        if crop is not None:
-            if len(self.plan.inputs) != 1 or u8_norm is None:
-                raise ValueError('the crop front end feeds a single uint8 image input')
-            v0 = self.plan.inputs[0]
-            if tuple(v0.shape[-3:]) != (crop.OH, crop.OW, 3) or int(np.prod(v0.shape[:-3], dtype=np.int64)) != crop.per_item:
-                raise ValueError('crops of %d x [%d, %d, 3] do not fill the model input %s' %
-                                 (crop.per_item, crop.OH, crop.OW, tuple(v0.shape)))
-        total = arrays[0].shape[0] if crop is None else crop.total
+        feed = crop if crop is not None else ArrayFeed(self.plan, arrays)
+        total = feed.total
         bs = int(min(bs, total))
-        nchunks = (total + bs - 1) // bs
+        nchunks = -(-total // bs)
         with torch.cuda.device(self.device):
-            if self.bound:
-                self.sync_weights()
-            with torch.cuda.stream(self.stream):
-                bp = self.bind(bs, u8_norm=u8_norm)
-            if self._wstamp is None:
-                self._wstamp = self._weight_stamp()
+            bp = self._begin(bs, u8_norm)
             if getattr(self, 'copy_stream', None) is None:
                 self.copy_stream = shared_stream(self.device, 'copy')
-            want = torch.uint8 if bp.u8 is not None else torch.float32
-            slot_bytes = sum(bs * int(np.prod(v.shape)) for v in self.plan.inputs) * (1 if want == torch.uint8 else 4)
-            depth = max(2, min(nchunks, int(os.environ.get('DEEPHAR_PREDICT_DEPTH', '8')),
-                               max(2, (512 << 20) // max(slot_bytes, 1))))
-            io = self._io(bp, depth, staged=crop is None)
-            on_gpu = crop is not None and crop.program == 'device'
-            if crop is not None:        # (the size query refuses a window beyond the scale cap before anything is enqueued)
-                nprog_max = max(crop.program_bytes(c0, min(bs, total - c0)) for c0 in range(0, total, bs))
-                if on_gpu:
-                    self._crop_slots_device(io, depth, 24 * bs * crop.per_item, crop.max_bytes(bs))
-                    srcs_dev = crop.store.srcs_dev
-                else:
-                    self._crop_slots(io, depth, nprog_max)
-            io['pending'] = [None] * len(io['pending'])        # a call that died mid-loop must not leak rows into this one
-            results = []
-            ahead = min(2, depth - 1)                           # chunks staged ahead of the one being enqueued
+            depth = ring_depth(nchunks, feed.slot_bytes(bs, u8_norm is not None))
+            feed.open(self, bp, bs, depth)
+            ring = bp.ring
+            ring.grow(depth)
+            ring.abandon(self.stream)
+            while len(bp.h2d) < depth:
+                bp.h2d.append(torch.cuda.Event())
+            results, staged = [], {}
             pool = _staging_pool()
-            staged = {}
+            ahead = chunk_steps(total, bs, depth)               # the same sequence, read min(2, depth - 1) chunks ahead of
+                                                                # the one being enqueued: the chunks staged by then
 
-            def collect(slot):
-                m = io['pending'][slot]
-                if m is not None:
-                    io['done'][slot].synchronize()
-                    results.append(self._host_outputs(bp, io['host_out'][slot], m))
-                    io['pending'][slot] = None
-
-            def stage(ci):
-                """Start the host-side copies of chunk ci into its slot; returns (m, on_dev, device sources, futures)."""
-                slot, start = ci % depth, ci * bs
-                collect(slot)                                   # chunk ci - depth used this slot (its H2D is long done)
-                m = min(bs, total - start)
-                if crop is not None:                            # the chunk's crop program, built off the main thread
-                    if on_gpu:
-                        return m, None, None, [pool.submit(crop.stage, start, m, io['jobs_host'][slot])]
-                    return m, None, None, [pool.submit(crop.build, start, m, io['prog_host'][slot])]
-                on_dev, dev_src, futs = [], [], []
-                for k, (v, arr) in enumerate(zip(self.plan.inputs, arrays)):
-                    part = arr[start:start + m]
-                    if tuple(part.shape[1:]) != tuple(v.shape):
-                        raise ValueError('input has shape %s, model expects [N, %s]' % (tuple(arr.shape), tuple(v.shape)))
-                    src = torch.from_numpy(np.ascontiguousarray(part)) if isinstance(part, np.ndarray) else part
-                    if (src.dtype == torch.uint8) != (want == torch.uint8):
-                        raise ValueError('plan bound for %s inputs, got %s' % (want, src.dtype))
-                    on_dev.append(bool(src.is_cuda))
-                    dev_src.append(src if src.is_cuda else None)
-                    if not src.is_cuda:                         # host-side cast (f64 -> f32) + pin, row slices in parallel
-                        dst = io['host_in'][slot][k]
-                        nsl = max(1, min(_STAGING_THREADS, src.numel() * src.element_size() >> 22, m))
-                        step = -(-m // nsl)
-                        for a0 in range(0, m, step):
-                            a1 = min(a0 + step, m)              # a ragged last chunk: both slices stop at m
-                            futs.append(pool.submit(dst[a0:a1].copy_, src[a0:a1]))
-                return m, on_dev, dev_src, futs
+            def stage(step):
+                """Start the host-side staging of a chunk into its slot; staged[ci] = the futures."""
+                _, _, ci, slot, start, m = step
+                ring.reclaim(slot, results)                     # chunk ci - depth used this slot (its H2D is long done)
+                staged[ci] = feed.stage_chunk(pool, slot, start, m)
 
             try:
-                for ci in range(min(ahead, nchunks)):
-                    staged[ci] = stage(ci)
-                for ci in range(nchunks):
-                    if ci + ahead < nchunks:
-                        staged[ci + ahead] = stage(ci + ahead)
-                    slot = ci % depth
-                    m, on_dev, dev_src, futs = staged.pop(ci)
-                    staged_now = [fu.result() for fu in futs]
-                    nprog = staged_now[0] if crop is not None else 0         # bytes of the chunk's crop program / job table
+                for step in itertools.islice(ahead, min(2, depth - 1)):
+                    stage(step)
+                for _, _, ci, slot, _, m in chunk_steps(total, bs, depth):
+                    for step in itertools.islice(ahead, 1):
+                        stage(step)
+                    done = [fu.result() for fu in staged.pop(ci)]
                     with torch.cuda.stream(self.copy_stream):
-                        if on_gpu:
-                            io['jobs_dev'][slot][:nprog].copy_(io['jobs_host'][slot][:nprog], non_blocking=True)
-                        elif crop is not None:
-                            io['prog_dev'][slot][:nprog].copy_(io['prog_host'][slot][:nprog], non_blocking=True)
-                        elif any(on_dev):                         # the caller's device data may still be in flight on ITS stream
-                            self.copy_stream.wait_stream(torch.cuda.current_stream())
-                        for k in range(len(arrays) if crop is None else 0):
-                            src = dev_src[k] if on_dev[k] else io['host_in'][slot][k][:m]
-                            io['dev_in'][slot][k][:m].copy_(src, non_blocking=True)
-                        io['h2d'][slot].record(self.copy_stream)
+                        feed.upload(slot, m, done, self.copy_stream)
+                        bp.h2d[slot].record(self.copy_stream)
                     with torch.cuda.stream(self.stream):
-                        self.stream.wait_event(io['h2d'][slot])                       # GPU-side wait
-                        for k, v in enumerate(self.plan.inputs):
-                            dst = bp.u8[id(v.buf)][0] if bp.u8 is not None else bp.tensor(v)
-                            if crop is not None:                # no intermediate tensor: the launch fills the plan's input
-                                prog = io['prog_built' if on_gpu else 'prog_dev'][slot]
-                                if on_gpu:                      # the program from the jobs, on this stream, in front of the launch
-                                    _lib.check(bp.lib.dh_crop_program_build_dev(
-                                        srcs_dev.data_ptr(), len(crop.store), io['jobs_dev'][slot].data_ptr(), m * crop.per_item,
-                                        crop.OH, crop.OW, prog.data_ptr(), prog.numel(), None, self.stream_ptr),
-                                        'dh_crop_program_build_dev')
-                                _lib.check(bp.lib.dh_crop_resize_u8(prog.data_ptr(), m * crop.per_item, crop.OH,
-                                                                    crop.OW, dst.data_ptr(), crop.OH * crop.OW * 3,
-                                                                    self.stream_ptr), 'dh_crop_resize_u8')
-                                continue
-                            dst[:m].copy_(io['dev_in'][slot][k][:m], non_blocking=True)
+                        self.stream.wait_event(bp.h2d[slot])                          # GPU-side wait
+                        feed.fill(slot, m)
                         self.forward(bp)
-                        io['host_out'][slot].copy_(bp.arena[:io['host_out'][slot].numel()], non_blocking=True)
-                        io['done'][slot].record(self.stream)
-                    io['pending'][slot] = m
+                        ring.submit(slot, m, self.stream)
                     if verbose:
                         print('%d/%d' % (min((ci + 1) * bs, total), total))
-                for k in range(depth):                                  # oldest pending chunk first
-                    collect((nchunks + k) % depth)
+                ring.drain(nchunks, depth, results)
             finally:
-                for _, _, _, futs in staged.values():                   # (an exception mid-loop: let the copies finish)
+                for futs in staged.values():                            # (an exception mid-loop: let the copies finish)
                     for fu in futs:
                         fu.cancel() or fu.exception()
-                if any(p is not None for p in io['pending']):
-                    self.stream.synchronize()
-                    io['pending'] = [None] * len(io['pending'])
+                ring.abandon(self.stream)
         nres = len(self.plan.outputs)
         return [np.concatenate([r[k] for r in results], axis=0) if len(results) > 1 else results[0][k]
                 for k in range(nres)]
@@ -1018,22 +1050,17 @@ class Executor:
         first launch and the final drain other than the recycling of output slots.
           once      : bbox0 (float64 [N, 4]) and the frame indices go to the device; dh_jobs_from_boxes_f64 makes iteration 0's
                       slice of the job table int32 [num_iter, N, 6].
-          chunk-step: dh_crop_program_build_dev from the resident slice of the job table (per-job status into int32
-                      [num_iter, N]), dh_crop_resize_u8 into the plan's uint8 input, the forward, the packed-output D2H into
-                      the slot; then, but for the last iteration, dh_refine_boxes_f64 reads output `outidx` where it lies in
-                      the arena and writes the chunk's rows of the box table and of the next iteration's job table.
+          chunk-step: crop_step from the resident slice of the job table (per-job status into int32 [num_iter, N]) into the
+                      plan's uint8 input, the forward, the packed-output D2H into the slot; then, but for the last iteration,
+                      dh_refine_boxes_f64 reads output `outidx` where it lies in the arena and writes the chunk's rows of the
+                      box table and of the next iteration's job table.
           Iteration t + 1 of a chunk depends only on iteration t of the same chunk, and both are on this stream: no event.
-        One program buffer serves every chunk-step (its only reader is the crop launch right behind the builder).
         Returns (raw output `outidx` per iteration: list of float32 [N, J, D]; the job tables int32 [num_iter, N, 6]; the
         builder's status int32 [num_iter, N]).  A refused job leaves its input frame as the previous chunk-step left it."""
         torch = _torch()
         lib = _lib.load()
-        OH, OW = int(out_hw[0]), int(out_hw[1])
-        if len(self.plan.inputs) != 1 or u8_norm is None or tuple(self.plan.inputs[0].shape) != (OH, OW, 3):
-            raise ValueError('the device refinement loop feeds a single uint8 image input [%d, %d, 3]' % (OH, OW))
-        if not 0 <= outidx < len(self.plan.outputs) or len(self.plan.outputs[outidx].shape) != 2 or \
-                self.plan.outputs[outidx].shape[-1] < 2:
-            raise ValueError('output %d is no pose output [J, D >= 2]' % outidx)
+        OH, OW, _ = frontend.image_io(self.plan.inputs, u8_norm is not None, self.plan.outputs, outidx, clips=False,
+                                      out_hw=out_hw, who='the device refinement loop')
         index = np.ascontiguousarray(index, np.int32)
         bbox0 = np.ascontiguousarray(bbox0, np.float64)
         total = index.shape[0]
@@ -1042,39 +1069,17 @@ class Executor:
         if index.min() < 0 or index.max() >= len(store):
             raise ValueError('frame index outside the %d stored frames' % len(store))
         bs = int(min(bs, total))
-        nchunks = (total + bs - 1) // bs
-        vout = self.plan.outputs[outidx]
-        J = vout.shape[0]
+        nchunks = -(-total // bs)
+        J = self.plan.outputs[outidx].shape[0]
         with torch.cuda.device(self.device):
-            if self.bound:
-                self.sync_weights()
-            with torch.cuda.stream(self.stream):
-                bp = self.bind(bs, u8_norm=u8_norm)
-            if self._wstamp is None:
-                self._wstamp = self._weight_stamp()
-            depth = max(2, min(num_iter * nchunks, int(os.environ.get('DEEPHAR_PREDICT_DEPTH', '8'))))
-            io = self._io(bp, depth, staged=False)
-            nbytes = C.c_size_t(0)
-            rc = lib.dh_crop_program_max_bytes(bs, len(store), OH, OW, C.byref(nbytes))
-            if rc == -2:
-                raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % bs)
-            _lib.check(rc, 'dh_crop_program_max_bytes')
-            if io.get('refine_prog') is None or io['refine_prog'].numel() < nbytes.value:
-                io['refine_prog'] = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            prog = io['refine_prog']
-            srcs_dev = store.srcs_dev
-            io['pending'] = [None] * len(io['pending'])
+            bp = self._begin(bs, u8_norm)
+            depth = ring_depth(num_iter * nchunks)
+            self.crop_room(bp, store, bs, OH, OW)
+            ring = bp.ring
+            ring.grow(depth)
+            ring.abandon(self.stream)
             results = []
-            pose = bp.tensor(vout)
-            dst = bp.u8[id(self.plan.inputs[0].buf)][0]
-
-            def collect(slot):
-                m = io['pending'][slot]
-                if m is not None:
-                    io['done'][slot].synchronize()
-                    results.append(self._host_outputs(bp, io['host_out'][slot], m)[outidx])
-                    io['pending'][slot] = None
-
+            pose = bp.tensor(self.plan.outputs[outidx])
             try:
                 with torch.cuda.stream(self.stream):
                     boxes = torch.from_numpy(bbox0).to(self.device, non_blocking=True)
@@ -1083,20 +1088,11 @@ class Executor:
                     status = torch.empty((num_iter, total), dtype=torch.int32, device=self.device)
                     _lib.check(lib.dh_jobs_from_boxes_f64(boxes.data_ptr(), src.data_ptr(), total, jobs.data_ptr(), self.stream_ptr),
                                'dh_jobs_from_boxes_f64')
-                    for step in range(num_iter * nchunks):
-                        t, ci = divmod(step, nchunks)
-                        slot, start = step % depth, ci * bs
-                        m = min(bs, total - start)
-                        collect(slot)                           # chunk-step `step - depth` used this slot
-                        _lib.check(lib.dh_crop_program_build_dev(
-                            srcs_dev.data_ptr(), len(store), jobs[t, start].data_ptr(), m, OH, OW, prog.data_ptr(), prog.numel(),
-                            status[t, start:].data_ptr(), self.stream_ptr), 'dh_crop_program_build_dev')
-                        _lib.check(lib.dh_crop_resize_u8(prog.data_ptr(), m, OH, OW, dst.data_ptr(), OH * OW * 3, self.stream_ptr),
-                                   'dh_crop_resize_u8')
+                    for _, t, _, slot, start, m in chunk_steps(total, bs, depth, num_iter):
+                        ring.reclaim(slot, results, outidx)     # chunk-step `step - depth` used this slot
+                        self.crop_step(bp, store, jobs[t, start].data_ptr(), m, OH, OW, status[t, start:].data_ptr())
                         self.forward(bp)
-                        io['host_out'][slot].copy_(bp.arena[:io['host_out'][slot].numel()], non_blocking=True)
-                        io['done'][slot].record(self.stream)
-                        io['pending'][slot] = m
+                        ring.submit(slot, m, self.stream)
                         if t + 1 < num_iter:                    # the chunk's next windows, from the poses in the arena
                             _lib.check(lib.dh_refine_boxes_f64(
                                 pose.data_ptr(), pose.stride(0), pose.stride(1), J, jobs[t, start].data_ptr(),
@@ -1104,12 +1100,9 @@ class Executor:
                                 jobs[t + 1, start].data_ptr(), self.stream_ptr), 'dh_refine_boxes_f64')
                     jobs_host = jobs.cpu().numpy()              # one copy each, behind everything on the stream
                     status_host = status.cpu().numpy()
-                for k in range(depth):                          # oldest pending chunk-step first
-                    collect((num_iter * nchunks + k) % depth)
+                ring.drain(num_iter * nchunks, depth, results, outidx)
             finally:
-                if any(p is not None for p in io['pending']):
-                    self.stream.synchronize()
-                    io['pending'] = [None] * len(io['pending'])
+                ring.abandon(self.stream)
         raw = [np.concatenate(results[t * nchunks:(t + 1) * nchunks], axis=0) if nchunks > 1 else results[t * nchunks]
                for t in range(num_iter)]
         return raw, jobs_host, status_host
@@ -1124,31 +1117,20 @@ class Executor:
         packed-output transfer -- 52 bytes per item leave the device, once, at the end.
           once     : the job table int32 [N * per_item, 6] goes to the device (index [N]: per_item = 1; index [N, T] of a clip
                      model: per_item = T, the item's window broadcast over its frames).
-          per chunk: dh_crop_program_build_dev from the resident slice of the job table (per-job status kept),
-                     dh_crop_resize_u8 into the plan's uint8 input, the forward, then dh_pose_boxes_f64 reads output `outidx`
-                     where it lies in the arena (confidence channel D - 2) and the item's window at jobs[i * per_item], and
-                     writes the chunk's rows of the box and status tables.  The forward joins its side streams before it
-                     returns, so output `outidx` is complete on this stream: no event, as in run_refine.
+          per chunk: crop_step from the resident slice of the job table (per-job status kept) into the plan's uint8 input, the
+                     forward, then dh_pose_boxes_f64 reads output `outidx` where it lies in the arena (confidence channel
+                     D - 2) and the item's window at jobs[i * per_item], and writes the chunk's rows of the box and status
+                     tables.  The forward joins its side streams before it returns, so output `outidx` is complete on this
+                     stream: no event, as in run_refine.
           at the end: one copy each of the int32 boxes, the float64 boxes, the statuses and the builder's statuses into pinned
                      memory, behind everything on the stream, and ONE drain.
-        One program buffer serves every chunk (its only reader is the crop launch right behind the builder).
         Returns (boxes int32 [N, 4], boxes float64 [N, 4], status int32 [N], the builder's status int32 [N, per_item]).  A
         refused job leaves its input frame as the previous chunk left it; the caller raises for it."""
         torch = _torch()
         lib = _lib.load()
-        OH, OW = int(out_hw[0]), int(out_hw[1])
-        if len(self.plan.inputs) != 1:
-            raise ValueError('the device box pass feeds a single image input, the plan has %d inputs' % len(self.plan.inputs))
-        in_shape = tuple(self.plan.inputs[0].shape)
-        if u8_norm is None or len(in_shape) not in (3, 4) or in_shape[-3:] != (OH, OW, 3):
-            raise ValueError('the device box pass feeds a uint8 image input [(T,) %d, %d, 3], not %s' % (OH, OW, in_shape))
-        per_item = 1 if len(in_shape) == 3 else int(in_shape[0])
-        nout = len(self.plan.outputs)
-        if not -nout <= outidx < nout:
-            raise ValueError('output %d of %d' % (outidx, nout))
+        OH, OW, per_item = frontend.image_io(self.plan.inputs, u8_norm is not None, self.plan.outputs, outidx, out_hw=out_hw,
+                                             who='the device box pass')
         vout = self.plan.outputs[outidx]
-        if len(vout.shape) != len(in_shape) - 1 or vout.shape[-1] < 2 or (per_item > 1 and vout.shape[0] != per_item):
-            raise ValueError('output %d %s is no pose output [(T,) J, D >= 2]' % (outidx, tuple(vout.shape)))
         index = np.ascontiguousarray(index, np.int32)
         windows = np.ascontiguousarray(windows, np.int32)
         total = index.shape[0]
@@ -1162,31 +1144,16 @@ class Executor:
         bs = int(min(bs, total))
         J, D = int(vout.shape[-2]), int(vout.shape[-1])
         with torch.cuda.device(self.device):
-            if self.bound:
-                self.sync_weights()
-            with torch.cuda.stream(self.stream):
-                bp = self.bind(bs, u8_norm=u8_norm)
-            if self._wstamp is None:
-                self._wstamp = self._weight_stamp()
-            nbytes = C.c_size_t(0)
-            rc = lib.dh_crop_program_max_bytes(bs * per_item, len(store), OH, OW, C.byref(nbytes))
-            if rc == -2:
-                raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % (bs * per_item))
-            _lib.check(rc, 'dh_crop_program_max_bytes')
-            io = self._io(bp, 0, staged=False)                      # (no output slots: nothing is packed out)
-            if io.get('boxes_prog') is None or io['boxes_prog'].numel() < nbytes.value:
-                io['boxes_prog'] = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-            prog = io['boxes_prog']
-            if io.get('boxes_host') is None or io['boxes_host'][0].shape[0] < total:     # pinned result tables, grown only
-                io['boxes_host'] = [torch.empty(shape, dtype=dt, pin_memory=True) for shape, dt in
-                                    (((total, 4), torch.int32), ((total, 4), torch.float64), ((total,), torch.int32),
-                                     ((total, per_item), torch.int32))]
-            host = [h[:total] for h in io['boxes_host']]
-            srcs_dev = store.srcs_dev
+            bp = self._begin(bs, u8_norm)
+            self.crop_room(bp, store, bs * per_item, OH, OW)
+            if bp.boxes_host is None or bp.boxes_host[0].shape[0] < total:               # pinned result tables, grown only
+                bp.boxes_host = [torch.empty(shape, dtype=dt, pin_memory=True) for shape, dt in
+                                 (((total, 4), torch.int32), ((total, 4), torch.float64), ((total,), torch.int32),
+                                  ((total, per_item), torch.int32))]
+            host = [h[:total] for h in bp.boxes_host]
             pose = bp.tensor(vout)                                  # [bs, (T,) J, D] where the forward leaves it
             item_stride = pose.stride(0)
             frame_stride = pose.stride(1) if per_item > 1 else item_stride
-            dst = bp.u8[id(self.plan.inputs[0].buf)][0]
             try:
                 with torch.cuda.stream(self.stream):
                     jobs = torch.from_numpy(table).to(self.device, non_blocking=True)
@@ -1194,13 +1161,8 @@ class Executor:
                     boxes_f = torch.empty((total, 4), dtype=torch.float64, device=self.device)
                     status = torch.empty((total,), dtype=torch.int32, device=self.device)
                     built = torch.zeros((total, per_item), dtype=torch.int32, device=self.device)
-                    for start in range(0, total, bs):
-                        m = min(bs, total - start)
-                        _lib.check(lib.dh_crop_program_build_dev(
-                            srcs_dev.data_ptr(), len(store), jobs[start].data_ptr(), m * per_item, OH, OW, prog.data_ptr(),
-                            prog.numel(), built[start].data_ptr(), self.stream_ptr), 'dh_crop_program_build_dev')
-                        _lib.check(lib.dh_crop_resize_u8(prog.data_ptr(), m * per_item, OH, OW, dst.data_ptr(), OH * OW * 3,
-                                                         self.stream_ptr), 'dh_crop_resize_u8')
+                    for _, _, _, _, start, m in chunk_steps(total, bs, 1):
+                        self.crop_step(bp, store, jobs[start].data_ptr(), m * per_item, OH, OW, built[start].data_ptr())
                         self.forward(bp)
                         _lib.check(lib.dh_pose_boxes_f64(
                             pose.data_ptr(), item_stride, frame_stride, pose.stride(-2), per_item, J, D - 2,
@@ -1228,11 +1190,7 @@ class Executor:
         m = tensors[0].shape[0]
         n = n or m
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
-            if self.bound:
-                self.sync_weights()
-            bp = self.bind(n)
-            if self._wstamp is None:
-                self._wstamp = self._weight_stamp()
+            bp = self._begin(n)
             for v, t in zip(self.plan.inputs, tensors):
                 dst = bp.tensor(v)[:m] if m <= bp.n else None
                 if dst is None or t.shape[0] != m or t.numel() != dst.numel() or \

@@ -56,6 +56,46 @@ def crop_afmat(box, out_wh, hflip=False):
     return np.dot(scale(1 / ow, 1 / oh), A)
 
 
+def image_io(inputs, u8=True, outputs=None, outidx=None, clips=True, out_hw=None, who='the crop front end'):
+    """What the frame front ends feed, stated once: a single uint8 image input [(T,) H, W, 3] per item (clips=False: [H, W, 3]
+    only; out_hw: of that very size) and, where `outidx` is given, a pose output [(T,) J, D >= 2] at that index of `outputs`.
+    `inputs` / `outputs`: a Model's or a Plan's (anything with a per-item .shape).  Returns (OH, OW, per_item)."""
+    if len(inputs) != 1:
+        raise ValueError('%s needs a single image input, got %d inputs' % (who, len(inputs)))
+    shape = tuple(inputs[0].shape)
+    if not u8 or len(shape) not in ((3, 4) if clips else (3,)) or shape[-1] != 3:
+        raise ValueError('%s needs a uint8 image input [%sH, W, 3], not %s%s' %
+                         (who, '(T,) ' if clips else '', '' if u8 else 'float32 ', shape))
+    OH, OW = int(shape[-3]), int(shape[-2])
+    if out_hw is not None and (int(out_hw[0]), int(out_hw[1])) != (OH, OW):
+        raise ValueError('%s: crops of [%d, %d, 3] do not fill the input %s' % (who, out_hw[0], out_hw[1], shape))
+    per_item = 1 if len(shape) == 3 else int(shape[0])
+    if outidx is not None:
+        if not -len(outputs) <= outidx < len(outputs):
+            raise ValueError('output %d of %d' % (outidx, len(outputs)))
+        vout = tuple(outputs[outidx].shape)
+        if len(vout) != len(shape) - 1 or vout[-1] < 2 or (per_item > 1 and vout[0] != per_item):
+            raise ValueError('output %d %s is no pose output [(T,) J, D >= 2]' % (outidx, vout))
+    return OH, OW, per_item
+
+
+def refused_window(status, where=''):
+    """The ValueError for a window the crop-program builder refuses (its status: -2 beyond the scale cap, else a bad box)."""
+    what = 'empty crop box' if status != -2 else \
+        'a crop window is more than 16 times its output on one axis (or the output row does not fit LDS)'
+    return ValueError(what + (': ' + where if where else ''))
+
+
+def crop_program_max_bytes(lib, njobs, nsrc, OH, OW):
+    """What the device program of `njobs` crops can take (dh_crop_program_max_bytes): allocated before the boxes are known."""
+    nbytes = C.c_size_t(0)
+    rc = lib.dh_crop_program_max_bytes(njobs, nsrc, OH, OW, C.byref(nbytes))
+    if rc == -2:
+        raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % njobs)
+    _lib.check(rc, 'dh_crop_program_max_bytes')
+    return nbytes.value
+
+
 class FrameStore:
     """Full frames resident on the device: each uint8 [H, W, 3] frame is uploaded once; frames may differ in size."""
 
@@ -89,12 +129,15 @@ class FrameStore:
 
 
 class CropFeed:
-    """What Executor.run_pipelined needs to crop its own input: the per-chunk crop programs over a FrameStore."""
+    """What Executor.run_pipelined needs to crop its own input: the per-chunk crop programs over a FrameStore, as a feed
+    (stage_chunk / upload / fill per chunk after slot_bytes and open: engine/executor.py, ArrayFeed)."""
 
     def __init__(self, store, index, boxes, hflip, out_hw, program='host'):
         if program not in ('host', 'device'):
             raise ValueError("program must be 'host' or 'device', got %r" % (program,))
         self.store, self.lib, self.program = store, _lib.load(), program
+        # chosen here, once: what a chunk stages into its slot (its job table / its program) and what fills the plan's input
+        self._stage, self.fill = (self.stage, self._fill_built) if program == 'device' else (self.build, self._fill_uploaded)
         self.index = np.asarray(index, np.int64)
         self.boxes = np.asarray(boxes, np.int64)
         self.hflip = np.asarray(hflip).astype(bool)
@@ -107,7 +150,7 @@ class CropFeed:
         if self.total and (self.index.min() < 0 or self.index.max() >= len(store)):
             raise ValueError('frame index outside the %d stored frames' % len(store))
         if np.any(self.boxes[..., 2] <= self.boxes[..., 0]) or np.any(self.boxes[..., 3] <= self.boxes[..., 1]):
-            raise ValueError('empty crop box')
+            raise refused_window(-1)
         flat = np.concatenate([self.index.reshape(-1, 1), self.boxes.reshape(-1, 4), self.hflip.reshape(-1, 1)], axis=1)
         self.jobs = np.ascontiguousarray(flat.astype(np.int32))                       # == dh_crop_job[total * per_item]
 
@@ -120,7 +163,7 @@ class CropFeed:
         nbytes = C.c_size_t(0)
         rc = self.lib.dh_crop_program_bytes(jobs, n, len(self.store), self.OH, self.OW, C.byref(nbytes))
         if rc == -2:
-            raise ValueError('a crop window is more than 16 times its output on one axis (or the output row does not fit LDS)')
+            raise refused_window(rc)
         _lib.check(rc, 'dh_crop_program_bytes')
         return nbytes.value
 
@@ -137,12 +180,7 @@ class CropFeed:
     # ---- program='device': a chunk's staging is its job table, the program is built by the GPU
     def max_bytes(self, m):
         """What the device program of a chunk of m items can take (dh_crop_program_max_bytes)."""
-        nbytes = C.c_size_t(0)
-        rc = self.lib.dh_crop_program_max_bytes(m * self.per_item, len(self.store), self.OH, self.OW, C.byref(nbytes))
-        if rc == -2:
-            raise ValueError('the crop program of %d jobs does not fit 2^31 bytes' % (m * self.per_item))
-        _lib.check(rc, 'dh_crop_program_max_bytes')
-        return nbytes.value
+        return crop_program_max_bytes(self.lib, m * self.per_item, len(self.store), self.OH, self.OW)
 
     def stage(self, start, m, out):
         """The job table of items [start, start + m) -- 24 bytes per job, nothing else -- into the uint8 tensor `out`; returns
@@ -155,6 +193,45 @@ class CropFeed:
         out[:nbytes].copy_(torch.from_numpy(part.reshape(-1).view(np.uint8)))
         return nbytes
 
+    # ---- the feed of Executor.run_pipelined
+    def slot_bytes(self, bs, u8):
+        return 0                          # nothing of the model's input is staged: the crop launch writes it in place
+
+    def open(self, ex, bp, bs, depth):
+        """The checks against the plan's input; then per slot of bp.byte_slots pinned host memory for a chunk's crop program
+        (program='device': for its JOB table, and bp.crop_prog for the program the GPU builds) and its device twin."""
+        import torch
+        if (self.OH, self.OW, self.per_item) != image_io(ex.plan.inputs, bp.u8 is not None):
+            raise ValueError('crops of %d x [%d, %d, 3] do not fill the model input %s' %
+                             (self.per_item, self.OH, self.OW, tuple(ex.plan.inputs[0].shape)))
+        # (the size query refuses a window beyond the scale cap before anything is enqueued)
+        nbytes = max(self.program_bytes(c0, min(bs, self.total - c0)) for c0 in range(0, self.total, bs))
+        if self.program == 'device':
+            nbytes = 24 * bs * self.per_item
+            ex.crop_room(bp, self.store, bs * self.per_item, self.OH, self.OW)
+        for k in range(depth):
+            if k == len(bp.byte_slots):
+                bp.byte_slots.append(None)
+            if bp.byte_slots[k] is None or bp.byte_slots[k][0].numel() < nbytes:
+                bp.byte_slots[k] = (torch.empty(nbytes, dtype=torch.uint8, pin_memory=True),
+                                    torch.empty(nbytes, dtype=torch.uint8, device=ex.device))
+        self.ex, self.bp = ex, bp
+
+    def stage_chunk(self, pool, slot, start, m):
+        return [pool.submit(self._stage, start, m, self.bp.byte_slots[slot][0])]     # built / copied off the main thread
+
+    def upload(self, slot, m, staged, copy_stream):
+        host, dev = self.bp.byte_slots[slot]
+        dev[:staged[0]].copy_(host[:staged[0]], non_blocking=True)                   # the bytes `_stage` reported
+
+    def _fill_uploaded(self, slot, m):
+        dst = self.bp.input_bytes()
+        _lib.check(self.lib.dh_crop_resize_u8(self.bp.byte_slots[slot][1].data_ptr(), m * self.per_item, self.OH, self.OW,
+                                              dst.data_ptr(), self.OH * self.OW * 3, self.ex.stream_ptr), 'dh_crop_resize_u8')
+
+    def _fill_built(self, slot, m):      # the program from the slot's jobs, on the compute stream, in front of the launch
+        self.ex.crop_step(self.bp, self.store, self.bp.byte_slots[slot][1].data_ptr(), m * self.per_item, self.OH, self.OW)
+
 
 def refine_from_frames(model, frames, index, bbox0, outidx, num_iter=2, winsize_scale=1.50, momentum=0.8, batch_size=8):
     """The box-refinement loop of evaltools.refine_pred_frames with the boxes resident on the GPU (Executor.run_refine): every
@@ -163,13 +240,7 @@ def refine_from_frames(model, frames, index, bbox0, outidx, num_iter=2, winsize_
     Returns (raw output `outidx` per iteration, crop-normalised; the integer windows [num_iter, N, 4] every iteration
     cropped; their crop_afmat maps [num_iter, N, 3, 3]).  ValueError, after the drain, for the first window the program builder
     refused: the errors CropFeed raises on the host for the same window."""
-    if len(model.inputs) != 1:
-        raise ValueError('refine_from_frames needs a model with a single image input, %s has %d inputs' %
-                         (model.name, len(model.inputs)))
-    shape = tuple(model.inputs[0].shape)
-    if len(shape) != 3 or shape[-1] != 3:
-        raise ValueError('refine_from_frames needs a single-image input [H, W, 3], the model takes %s' % (shape,))
-    OH, OW = shape[0], shape[1]
+    OH, OW, _ = image_io(model.inputs, clips=False, who='refine_from_frames of %s' % model.name)
     ex = model.executor
     store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
     total = len(index)
@@ -179,10 +250,7 @@ def refine_from_frames(model, frames, index, bbox0, outidx, num_iter=2, winsize_
     bad = np.argwhere(status != 0)
     if len(bad):
         t, i = (int(v) for v in bad[0])
-        if status[t, i] == -2:
-            raise ValueError('a crop window is more than 16 times its output on one axis (or the output row does not fit LDS): '
-                             'iteration %d, sample %d, window %s' % (t, i, jobs[t, i, 1:5].tolist()))
-        raise ValueError('empty crop box: iteration %d, sample %d, window %s' % (t, i, jobs[t, i, 1:5].tolist()))
+        raise refused_window(status[t, i], 'iteration %d, sample %d, window %s' % (t, i, jobs[t, i, 1:5].tolist()))
     windows = jobs[:, :, 1:5].astype(np.int64)
     afmat = np.zeros((num_iter, total, 3, 3))
     for pos in np.ndindex(num_iter, total):
@@ -199,18 +267,13 @@ def frame_boxes_from_frames(model, frames, index, windows, outidx=-1, scale=1.5,
     Returns (boxes int64 [N, 4] -- get_bbox_from_poses(...).astype(int); boxes float64 [N, 4]; status int32 [N]: 0 ok, 1 a frame
     keeps no joint, 2 a kept joint is NaN, 3 a corner does not fit int32, 4 never here).  ValueError, after the drain, for the
     first window the program builder refused: the errors CropFeed raises on the host for the same window."""
-    if len(model.inputs) != 1:
-        raise ValueError('frame_boxes_from_frames needs a model with a single image input, %s has %d inputs' %
-                         (model.name, len(model.inputs)))
-    shape = tuple(model.inputs[0].shape)
-    if len(shape) not in (3, 4) or shape[-1] != 3:
-        raise ValueError('frame_boxes_from_frames needs an image input [(T,) H, W, 3], the model takes %s' % (shape,))
+    OH, OW, _ = image_io(model.inputs, who='frame_boxes_from_frames of %s' % model.name)
     index = np.asarray(index, np.int64)
     windows = np.asarray(windows)
     if windows.dtype.kind not in 'iu':
         raise ValueError('windows must be integer windows (frontend.crop_box)')
-    if index.ndim != len(shape) - 2 or (len(shape) == 4 and index.shape[1] != shape[0]):
-        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, shape))
+    if index.ndim < 1 or index.shape[1:] != tuple(model.inputs[0].shape[:-3]):
+        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, tuple(model.inputs[0].shape)))
     total = index.shape[0]
     if windows.shape != (total, 4):
         raise ValueError('windows %s do not give one window for each of %d items' % (windows.shape, total))
@@ -218,7 +281,6 @@ def frame_boxes_from_frames(model, frames, index, windows, outidx=-1, scale=1.5,
         return np.zeros((0, 4), np.int64), np.zeros((0, 4)), np.zeros((0,), np.int32)
     if np.abs(windows).max() > 0x7fffffff:
         raise ValueError('a window corner does not fit int32')
-    OH, OW = shape[-3], shape[-2]
     ex = model.executor
     store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
     bs = int(min(batch_size or total, total))
@@ -226,10 +288,7 @@ def frame_boxes_from_frames(model, frames, index, windows, outidx=-1, scale=1.5,
     bad = np.argwhere(built != 0)
     if len(bad):
         i = int(bad[0][0])
-        if built[tuple(bad[0])] == -2:
-            raise ValueError('a crop window is more than 16 times its output on one axis (or the output row does not fit LDS): '
-                             'sample %d, window %s' % (i, windows[i].tolist()))
-        raise ValueError('empty crop box: sample %d, window %s' % (i, windows[i].tolist()))
+        raise refused_window(built[tuple(bad[0])], 'sample %d, window %s' % (i, windows[i].tolist()))
     return boxes.astype(np.int64), boxes_f64, status
 
 
@@ -247,24 +306,18 @@ def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32, 
     Bit for bit model.predict(<uint8 crops of the loader>, batch_size)."""
     if program not in ('host', 'device'):
         raise ValueError("program must be 'host' or 'device', got %r" % (program,))
-    if len(model.inputs) != 1:
-        raise ValueError('predict_from_frames needs a model with a single image input, %s has %d inputs' %
-                         (model.name, len(model.inputs)))
-    shape = tuple(model.inputs[0].shape)
-    if len(shape) not in (3, 4) or shape[-1] != 3:
-        raise ValueError('predict_from_frames needs an image input [(T,) H, W, 3], the model takes %s' % (shape,))
+    OH, OW, _ = image_io(model.inputs, who='predict_from_frames of %s' % model.name)
     index = np.asarray(index, np.int64)
     boxes = np.asarray(boxes)
     if boxes.dtype.kind not in 'iu':
         raise ValueError('boxes must be integer windows (frontend.crop_box)')
-    if index.ndim != len(shape) - 2 or (len(shape) == 4 and index.shape[1] != shape[0]):
-        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, shape))
-    if len(shape) == 4 and boxes.ndim == 2:
+    if index.ndim < 1 or index.shape[1:] != tuple(model.inputs[0].shape[:-3]):
+        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, tuple(model.inputs[0].shape)))
+    if index.ndim == 2 and boxes.ndim == 2:
         boxes = np.broadcast_to(boxes[:, None, :], index.shape + (4,))
     flips = np.zeros(index.shape, bool) if hflip is None else np.asarray(hflip).astype(bool)
     if flips.ndim < index.ndim:
         flips = np.broadcast_to(flips.reshape(flips.shape + (1,) * (index.ndim - flips.ndim)), index.shape)
-    OH, OW = shape[-3], shape[-2]
     afmat = np.zeros(index.shape + (3, 3))
     for pos in np.ndindex(*index.shape):
         afmat[pos] = crop_afmat(boxes[pos], (OW, OH), bool(flips[pos]))
