@@ -84,7 +84,11 @@ class CropJob(C.Structure):                      # == struct dh_crop_job
     _fields_ = [(n, i32) for n in ('src', 'x0', 'y0', 'x1', 'y1', 'hflip')]
 
 
-class SchedOp(C.Structure):                     # == struct dh_sched_op (dh_sched_build_ops)
+class VoteSrc(C.Structure):                      # == struct dh_vote_src (dh_vote_products_f64)
+    _fields_ = [('p', vp), ('item_stride', i64)]
+
+
+class SchedOp(C.Structure):                    # == struct dh_sched_op (dh_sched_build_ops)
     _fields_ = [(n, i32) for n in ('kind', 'stream', 'arg', 'entry')]
 
 
@@ -226,6 +230,8 @@ SIGNATURES = {
     'dh_pose_boxes_host': (C.c_int, [vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp, i64, C.c_int, C.c_double, vp, vp, vp]),
     'dh_frame_boxes_shape': (C.c_int, [C.c_int, C.c_int, i64] + [C.c_int] * 6 + [i64, C.c_int, C.POINTER(C.c_int)]),
     'dh_frame_boxes_host': (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 4 + [C.c_double, vp, vp, vp]),
+    'dh_vote_products_f64': (C.c_int, [C.POINTER(VoteSrc), C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    'dh_vote_products_host': (C.c_int, [C.POINTER(VoteSrc), C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]),
     'dh_sched_build_ops':(C.c_int, [C.c_int] + [C.POINTER(i32)] * 5 + [C.c_int] * 4 + [C.POINTER(SchedOp), C.c_int,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dh_unpack_cut_f32': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, C.c_int, vp]),

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
 SOURCES = ["conv_igemm.hip", "gemm1x1.hip", "convt2x2.hip", "convt2x2s.hip", "gemm1x1s.hip", "gemm1x1s_p2.hip", "gemm1x1s_p1.hip",
            "gemm1x1s_ext.hip", "gemm1x1s_ext_p2.hip", "gemm1x1s_ext_p1.hip", "conv_splitk.hip", "conv_halo.hip", "conv_stem.hip", "spatial.hip", "decoder.hip",
-           "capi.hip", "plan.hip", "clip.hip", "out_pack.hip", "crop.hip", "refine.hip", "posebox.hip"]
+           "capi.hip", "plan.hip", "clip.hip", "out_pack.hip", "crop.hip", "refine.hip", "posebox.hip", "vote.hip"]
 HEADERS = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(INCLUDE, "deephar_hip.h")]
 LIB = os.path.join(HERE, "libdeephar_hip.so")
 OBJDIR = os.path.join(HERE, "build")

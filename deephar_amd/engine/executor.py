@@ -223,6 +223,7 @@ class BoundPlan:
         # enqueued on that stream behind the forward's join -- what run_refine, run_frame_boxes and plan.hip (pl->crop_prog) rely on
         self.crop_prog = None
         self.boxes_host = None    # run_frame_boxes: the pinned result tables
+        self.votes_host = None    # run_votes: the pinned result tables
 
     # ---- views -------------------------------------------------------------------------------------------
     def ptr(self, v):
@@ -1173,6 +1174,91 @@ class Executor:
             finally:
                 self.stream.synchronize()                           # the one drain (and nothing in flight behind an exception)
         return tuple(h.numpy().copy() for h in host)
+
+    def run_votes(self, store, index, windows, hflip, seq, nseq, outidx_list, keep_scores, bs, u8_norm):
+        with self._lock:          # one thread at a time on the shared stream (engine/executor.py: stream_lock)
+            return self._run_votes_locked(store, index, windows, hflip, seq, nseq, outidx_list, keep_scores, bs, u8_norm)
+
+    def _run_votes_locked(self, store, index, windows, hflip, seq, nseq, outidx_list, keep_scores, bs, u8_norm):
+        """The multi-clip action vote (evaltools.action.multiclip_votes_frames) on the device: all N items (clips, as they are
+        or mirrored) as nchunks chunks on the compute stream, ONE stream of launches without a host wait in between and no
+        packed-output transfer.
+          once     : the job table int32 [N, per_item, 6] goes to the device (the item's window broadcast over its frames, its
+                     mirror flag in every job's hflip field), and so does seq; acc float64 [nb, nseq, C] is set to ones.
+          per chunk: crop_step from the resident slice of the job table (per-job status kept) into the plan's uint8 input, the
+                     forward, then ONE dh_vote_products_f64 call that reads the action outputs `outidx_list` where they lie in
+                     the arena and multiplies the chunk's rows into acc, with seq[start:].  Its label and score tables are dense
+                     per CALL, so the chunk's block [nb, m(, C)] lies at nb * start (* C) of a flat table and is put in place
+                     on the host.  The forward joins its side streams before it returns, so the outputs are complete on this
+                     stream: no event, as in run_frame_boxes.  A sequence may straddle chunks: the products stay in acc.
+          at the end: one copy each of acc, the labels, the builder's statuses and the optional scores into pinned memory,
+                     behind everything on the stream, and ONE drain.
+        Returns (a_pred float64 [nb, nseq, C], labels int32 [nb, N], scores float32 [nb, N, C] or None, the builder's status
+        int32 [N, per_item]).  A refused job leaves its input frame as the previous chunk left it; the caller raises for it."""
+        torch = _torch()
+        lib = _lib.load()
+        OH, OW, per_item = frontend.image_io(self.plan.inputs, u8_norm is not None, who='the device vote')
+        outs = [self.plan.outputs[k] for k in outidx_list]
+        if not outs or any(len(v.shape) != 1 or tuple(v.shape) != tuple(outs[0].shape) for v in outs):
+            raise ValueError('outputs %s are not action outputs of one shape (C,): %s' %
+                             (list(outidx_list), [tuple(v.shape) for v in outs]))
+        nb, C, nseq = len(outs), int(outs[0].shape[0]), int(nseq)
+        index = np.ascontiguousarray(index, np.int32)
+        windows = np.ascontiguousarray(windows, np.int32)
+        hflip = np.asarray(hflip).astype(bool)
+        seq = np.ascontiguousarray(seq, np.int32)
+        total = index.shape[0]
+        if total < 1 or index.shape != ((total,) if per_item == 1 else (total, per_item)) or windows.shape != (total, 4) or \
+                hflip.shape != (total,) or seq.shape != (total,):
+            raise ValueError('index %s, windows %s, hflip %s and seq %s do not describe items of %d frame(s)' %
+                             (index.shape, windows.shape, hflip.shape, seq.shape, per_item))
+        if index.min() < 0 or index.max() >= len(store):
+            raise ValueError('frame index outside the %d stored frames' % len(store))
+        if nseq < 1 or seq.min() < 0 or seq.max() >= nseq:
+            raise ValueError('seq outside [0, %d)' % nseq)
+        table = np.zeros((total, per_item, 6), np.int32)
+        table[:, :, 0] = index.reshape(total, per_item)
+        table[:, :, 1:5] = windows[:, None, :]
+        table[:, :, 5] = hflip[:, None]
+        bs = int(min(bs, total))
+        sizes = [(nb * nseq * C, torch.float64), (nb * total, torch.int32), (total * per_item, torch.int32)] + \
+            ([(nb * total * C, torch.float32)] if keep_scores else [])
+        with torch.cuda.device(self.device):
+            bp = self._begin(bs, u8_norm)
+            self.crop_room(bp, store, bs * per_item, OH, OW)
+            if bp.votes_host is None or len(bp.votes_host) < len(sizes) or \
+                    any(h.numel() < size for h, (size, _) in zip(bp.votes_host, sizes)):           # pinned result tables
+                bp.votes_host = [torch.empty(size, dtype=dt, pin_memory=True) for size, dt in sizes]
+            host = [h[:size] for h, (size, _) in zip(bp.votes_host, sizes)]
+            probs = [bp.tensor(v) for v in outs]                    # [bs, C] each, where the forward leaves them
+            srcs = (_lib.VoteSrc * nb)(*[_lib.VoteSrc(p.data_ptr(), max(p.stride(0), C)) for p in probs])
+            try:
+                with torch.cuda.stream(self.stream):
+                    jobs = torch.from_numpy(table).to(self.device, non_blocking=True)
+                    seq_dev = torch.from_numpy(seq).to(self.device, non_blocking=True)
+                    acc = torch.ones(nb * nseq * C, dtype=torch.float64, device=self.device)
+                    label = torch.empty(nb * total, dtype=torch.int32, device=self.device)
+                    built = torch.zeros(total * per_item, dtype=torch.int32, device=self.device)
+                    scores = torch.empty(nb * total * C, dtype=torch.float32, device=self.device) if keep_scores else None
+                    for _, _, _, _, start, m in chunk_steps(total, bs, 1):
+                        self.crop_step(bp, store, jobs[start].data_ptr(), m * per_item, OH, OW,
+                                       built[start * per_item:].data_ptr())
+                        self.forward(bp)
+                        _lib.check(lib.dh_vote_products_f64(
+                            srcs, nb, C, seq_dev[start:].data_ptr(), m, nseq, acc.data_ptr(), label[nb * start:].data_ptr(),
+                            scores[nb * start * C:].data_ptr() if keep_scores else None, self.stream_ptr), 'dh_vote_products_f64')
+                    for h, d in zip(host, (acc, label, built) + ((scores,) if keep_scores else ())):
+                        h.copy_(d, non_blocking=True)               # behind everything on the stream
+            finally:
+                self.stream.synchronize()                           # the one drain (and nothing in flight behind an exception)
+        a_pred = host[0].numpy().reshape(nb, nseq, C).copy()
+        labels = np.empty((nb, total), np.int32)
+        out_scores = np.empty((nb, total, C), np.float32) if keep_scores else None
+        for _, _, _, _, start, m in chunk_steps(total, bs, 1):      # every call's dense block into its columns
+            labels[:, start:start + m] = host[1].numpy()[nb * start:nb * (start + m)].reshape(nb, m)
+            if keep_scores:
+                out_scores[:, start:start + m] = host[3].numpy()[nb * start * C:nb * (start + m) * C].reshape(nb, m, C)
+        return a_pred, labels, out_scores, host[2].numpy().reshape(total, per_item).copy()
 
     def run_device(self, tensors, n=None, inputs_copied=None):
         with self._lock:         # one thread at a time on the shared stream (engine/executor.py: stream_lock)

@@ -19,3 +19,9 @@ penn_tools = SimpleNamespace(eval_singleclip_gt_bbox=action.eval_singleclip_gt_b
 ntu_tools = SimpleNamespace(eval_singleclip_gt_bbox_generator=action.eval_singleclip_gt_bbox_generator,
                             eval_multiclip_dataset=action.ntu_eval_multiclip_dataset)
 generic = SimpleNamespace(get_bbox_from_poses=bbox.get_bbox_from_poses)
+
+# the multi-clip vote over full frames (action.py) and the box dictionary -> clip window helpers it is fed by (bbox.py)
+vote_products = action.vote_products
+multiclip_votes_frames = action.multiclip_votes_frames
+compute_clip_bbox = bbox.compute_clip_bbox
+clip_window = bbox.clip_window

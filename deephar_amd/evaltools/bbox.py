@@ -138,6 +138,26 @@ def predict_frame_bboxes_frames(model, frames, index, windows, keys, scale=1.5, 
     return boxes
 
 
+def compute_clip_bbox(bbox_dict, seq_idx, frame_list):
+    """The box of a clip from per-frame predicted boxes (deephar/data/pennaction.py:33-44): the union of the boxes
+    bbox_dict['<seq_idx>.<frame>'] -- the dictionary predict_frame_bboxes(_frames) returns -- over the clip's frames, as a
+    float64 [x0, y0, x1, y1].  A frame without a box raises KeyError, as the reference's does."""
+    boxes = np.array([[np.inf, np.inf, -np.inf, -np.inf]] + [bbox_dict['%d.%d' % (seq_idx, f)] for f in frame_list], dtype=np.float64)
+    return np.concatenate([boxes[:, 0:2].min(axis=0), boxes[:, 2:4].max(axis=0)])
+
+
+def clip_window(bbox):
+    """The integer crop window the loaders give a box in test mode (pennaction.py:133-157, ntu.py:204-223: zero translation,
+    scale 1, angle 0): bbox_to_objposwin, a (32, 32) window when either side is below 32 pixels, then frontend.crop_box --
+    corners truncated toward zero.  compute_clip_bbox and this turn the box dictionary into the `windows` of
+    evaltools.action.multiclip_votes_frames."""
+    from .. import frontend
+    objpos, winsize = bbox_to_objposwin(bbox)
+    if min(winsize) < 32:
+        winsize = (32, 32)
+    return frontend.crop_box(objpos, winsize)
+
+
 def predict_frame_bboxes(model, ds, mode, scale=1.5, key=None):
     """The loop of exp/pennaction/predict_bboxes.py:53-68: one forward per sample, box from the predicted pose,
     integer box keyed '<seq_idx>.<frame>' (or key(data, i))."""

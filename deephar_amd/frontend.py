@@ -12,6 +12,8 @@ refine_from_frames runs the whole box-refinement loop with the boxes resident on
 forward, csrc/refine_index.h): the caller the device builder was made for.
 frame_boxes_from_frames is the per-frame person-box pass: the pose -> box step is one launch behind every forward
 (dh_pose_boxes_f64, csrc/posebox_index.h) and only the boxes leave the device.
+votes_from_frames is the multi-clip action vote: the product of the per-clip class probabilities is one launch behind every
+forward (dh_vote_products_f64, csrc/vote_index.h) and no model output leaves the device.
 
 Scope: the loaders' test-mode geometry -- angle 0, integer window, bilinear, optional mirror, 3 channels, uint8.  Box and
 matrix bookkeeping stays on the host in float64 (crop_box, crop_afmat), composed like deephar/utils/transform.py does.
@@ -290,6 +292,72 @@ def frame_boxes_from_frames(model, frames, index, windows, outidx=-1, scale=1.5,
         i = int(bad[0][0])
         raise refused_window(built[tuple(bad[0])], 'sample %d, window %s' % (i, windows[i].tolist()))
     return boxes.astype(np.int64), boxes_f64, status
+
+
+def vote_outputs(outputs, outidx=None):
+    """The action outputs a vote reads: `outidx` (None: all) as non-negative indices into `outputs`, which must all have the
+    same per-item shape (C,).  Returns (indices, C)."""
+    picked = list(range(len(outputs))) if outidx is None else [int(k) for k in outidx]
+    if not picked:
+        raise ValueError('no output to vote on')
+    for k in picked:
+        if not -len(outputs) <= k < len(outputs):
+            raise ValueError('output %d of %d' % (k, len(outputs)))
+    picked = [k % len(outputs) for k in picked]
+    shapes = [tuple(outputs[k].shape) for k in picked]
+    if any(len(s) != 1 or s != shapes[0] for s in shapes):
+        raise ValueError('outputs %s are not action outputs of one shape (C,): %s' % (picked, shapes))
+    return picked, int(shapes[0][0])
+
+
+def votes_from_frames(model, frames, index, windows, hflip, seq, nseq=None, outidx=None, keep_scores=False, batch_size=8):
+    """The multi-clip action vote with the vote on the GPU (Executor.run_votes): every chunk of items -- clips as they are or
+    mirrored -- is cropped out of the resident frames and predicted, and dh_vote_products_f64 multiplies its class probabilities
+    into the running products of the items' sequences where the forward left them (csrc/vote_index.h restates
+    evaltools.action.vote_products); no model output is copied to the host.
+    index [N] (image model) or [N, T] (clip model); windows: integer (x0, y0, x1, y1) per item as crop_box makes them, [N, 4],
+    broadcast over the item's frames; hflip: one mirror flag per item, [N]; seq: the sequence of every item, [N], in [0, nseq)
+    (nseq None: max(seq) + 1); outidx: the action outputs voted on (None: all), every one of per-item shape (C,).
+    Items are voted in their order; they need not be sorted by sequence.
+    Returns (a_pred float64 [nb, nseq, C]: the products; labels int32 [nb, N]: np.argmax of the item's sequence right after the
+    item; scores float32 [nb, N, C]: the per-item probabilities, or None without keep_scores).  ValueError, after the drain, for
+    the first window the program builder refused: the errors CropFeed raises on the host for the same window."""
+    image_io(model.inputs, who='votes_from_frames of %s' % model.name)
+    picked, C = vote_outputs(model.outputs, outidx)
+    index = np.asarray(index, np.int64)
+    windows = np.asarray(windows)
+    if windows.dtype.kind not in 'iu':
+        raise ValueError('windows must be integer windows (frontend.crop_box)')
+    if index.ndim < 1 or index.shape[1:] != tuple(model.inputs[0].shape[:-3]):
+        raise ValueError('index has shape %s, the model takes %s per item' % (index.shape, tuple(model.inputs[0].shape)))
+    total = index.shape[0]
+    hflip = np.asarray(hflip).astype(bool)
+    seq = np.asarray(seq)
+    if windows.shape != (total, 4) or hflip.shape != (total,) or seq.shape != (total,):
+        raise ValueError('windows %s, hflip %s and seq %s do not give one window, flag and sequence for each of %d items' %
+                         (windows.shape, hflip.shape, seq.shape, total))
+    if total and seq.dtype.kind not in 'iu':
+        raise ValueError('seq must be integers')
+    nseq = int(nseq) if nseq is not None else (int(seq.max()) + 1 if total else 0)
+    if total and (nseq < 1 or seq.min() < 0 or seq.max() >= nseq):
+        raise ValueError('seq outside [0, %d)' % nseq)
+    if total == 0:
+        return (np.ones((len(picked), max(nseq, 0), C)), np.zeros((len(picked), 0), np.int32),
+                np.zeros((len(picked), 0, C), np.float32) if keep_scores else None)
+    if np.abs(windows).max() > 0x7fffffff:
+        raise ValueError('a window corner does not fit int32')
+    ex = model.executor
+    store = frames if isinstance(frames, FrameStore) else FrameStore(frames, ex.device)
+    if index.min() < 0 or index.max() >= len(store):
+        raise ValueError('frame index outside the %d stored frames' % len(store))
+    bs = int(min(batch_size or total, total))
+    a_pred, labels, scores, built = ex.run_votes(store, index, windows, hflip, seq, nseq, picked, keep_scores, bs,
+                                                 model.channel_power)
+    bad = np.argwhere(built != 0)
+    if len(bad):
+        i = int(bad[0][0])
+        raise refused_window(built[tuple(bad[0])], 'item %d, window %s' % (i, windows[i].tolist()))
+    return a_pred, labels, scores
 
 
 def predict_from_frames(model, frames, index, boxes, hflip=None, batch_size=32, program='host'):

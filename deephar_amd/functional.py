@@ -301,6 +301,53 @@ def pose_boxes(poses, windows, scale=1.5, conf_channel=None):
     return boxes, boxes_f, status
 
 
+def vote_sources(probs, n, C):
+    """The dh_vote_src table of `probs` -- float32 CUDA tensors [n, C] with a unit class stride, any row stride (a view of a
+    plan's output is read where it lies) -- as a ctypes array."""
+    torch = _t()
+    srcs = (_lib.VoteSrc * len(probs))()
+    for b, p in enumerate(probs):
+        if not (torch.is_tensor(p) and p.is_cuda and p.dtype == torch.float32 and tuple(p.shape) == (n, C) and
+                (C == 1 or p.stride(1) == 1)):
+            raise ValueError('probs[%d] must be a float32 CUDA tensor [%d, %d] with a unit class stride' % (b, n, C))
+        srcs[b].p = p.data_ptr()
+        srcs[b].item_stride = p.stride(0) if n > 1 else max(p.stride(0), C)   # (torch gives a dimension of size 1 any stride)
+    return srcs
+
+
+def vote_products(probs, seq, nseq, acc=None, keep_scores=False):
+    """The multi-clip action vote on the GPU (dh_vote_products_f64), on torch's current stream: the device form of
+    evaltools.action.vote_products.  probs: a list of nb float32 CUDA tensors [n, C] (one per action output; row k is item k's
+    class probabilities; any row stride); seq: the sequence of every item, [n] (an int32 CUDA tensor, or anything np.asarray
+    takes); acc: the running products float64 CUDA [nb, nseq, C], multiplied IN PLACE (None: ones).  For k in order,
+    acc[b, seq[k]] *= probs[b][k] and label[b, k] = np.argmax(acc[b, seq[k]]); an item with seq[k] outside [0, nseq) is skipped
+    with label -1.  Returns (acc, label int32 [nb, n]) and, with keep_scores, scores float32 [nb, n, C], on the device."""
+    torch = _t()
+    probs = list(probs)
+    if not probs or not torch.is_tensor(probs[0]) or probs[0].dim() != 2:
+        raise ValueError('probs must be a non-empty list of float32 CUDA tensors [n, C]')
+    n, C = (int(v) for v in probs[0].shape)
+    nb, nseq, dev = len(probs), int(nseq), probs[0].device
+    srcs = vote_sources(probs, n, C)
+    if not torch.is_tensor(seq):
+        seq = torch.from_numpy(np.ascontiguousarray(seq, np.int32)).to(dev)
+    if not (seq.is_cuda and seq.dtype == torch.int32 and tuple(seq.shape) == (n,) and seq.is_contiguous()):
+        raise ValueError('seq must be int32 [%d]' % n)
+    if nseq < 1:
+        raise ValueError('nseq must be positive')
+    if acc is None:
+        acc = torch.ones((nb, nseq, C), dtype=torch.float64, device=dev)
+    if not (acc.is_cuda and acc.dtype == torch.float64 and tuple(acc.shape) == (nb, nseq, C) and acc.is_contiguous()):
+        raise ValueError('acc must be a contiguous float64 CUDA tensor [%d, %d, %d]' % (nb, nseq, C))
+    label = torch.empty((nb, n), dtype=torch.int32, device=dev)
+    scores = torch.empty((nb, n, C), dtype=torch.float32, device=dev) if keep_scores else None
+    rc = _lib.load().dh_vote_products_f64(srcs, nb, C, _p(seq), n, nseq, _p(acc), _p(label), _p(scores), _stream())
+    if rc == -1:
+        raise ValueError('vote_products: bad argument (no items, no classes, or a row stride smaller than the classes)')
+    _lib.check(rc, 'dh_vote_products_f64')
+    return (acc, label, scores) if keep_scores else (acc, label)
+
+
 def dwconv2d(x, dw_kernel, pre_scale=None, pre_shift=None, pre_relu=False, up_in=False):
     """Depthwise conv, stride 1, TF-SAME.  dw_kernel numpy [kh,kw,C,1].  up_in: x is at half resolution and the
     convolution runs on UpSampling2D((2, 2))(x) without writing it out (dh_dw_args.up_in)."""

@@ -852,6 +852,38 @@ int dh_frame_boxes_host(dh_plan* plan, const dh_frames* f, const int32_t* src, c
                         int32_t* status_out /* [n] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The multi-clip action vote on the device: the product of the per-clip class probabilities of every sequence and the running
+ * arg-max label behind every clip (exp/common/penn_tools.py:85-163, exp/common/ntu_tools.py:53-152 in the reference,
+ * deephar_amd/evaltools/action.py: _multiclip, vote_products, multiclip_votes_frames) as one small launch behind the forward, so
+ * that no model output leaves the device.  The arithmetic is csrc/vote_index.h: the same bits on the host (`_host` twin over host
+ * pointers) and on the device.
+ *   An ITEM k is one clip's result: nb rows of C float32 class probabilities, row k of output b at srcs[b].p + k *
+ *   srcs[b].item_stride (strides in floats: the launch reads a plan's outputs where they lie in the arena), of sequence seq[k].
+ *   `srcs` is a HOST table: it travels by value in the kernel arguments, at most 32 sources per launch, more as further launches
+ *   over disjoint b; nothing is uploaded per call and the launches are capturable.
+ *   For k = 0 .. n-1 IN THAT ORDER and every b:
+ *     acc[b, seq[k], c] *= (double)p_b[k, c]      one IEEE double multiply per class; the caller initialises acc to 1.0
+ *     label_out[b, k]    = argmax_c acc[b, seq[k], :] with np.argmax's rule: the first maximum wins, a NaN beats every number,
+ *                          the first NaN wins (+0 and -0 are equal)
+ *     scores_out[b, k, c] = p_b[k, c]             if scores_out is not NULL
+ *   Items need not be sorted by sequence.  Two calls over [0, n1) and [n1, n) with the same acc equal one call over [0, n) bit
+ *   for bit (label_out and scores_out are dense [nb, n(, C)] of EACH call).  There is no status word: products go subnormal,
+ *   reach zero or become inf * 0 = NaN as numpy's do; double denormals are not flushed.  seq is device data: an item whose
+ *   seq[k] is outside [0, nseq) is skipped -- label -1, acc and its scores_out rows untouched.
+ *   One wavefront per output b, lanes over the classes, a serial loop over the items, a cross-lane arg-max under a total order
+ *   (no order dependence).  No atomics; nothing allocates, nothing synchronises.
+ *   DH_EINVAL: NULL or misaligned pointers (acc to 8 bytes, the rest to 4; scores_out may be NULL); nb < 1, C < 1, n < 1,
+ *            nseq < 1; an item_stride < C or above 2^40; (n - 1) item_stride, nb nseq C or nb n C above 2^58.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct dh_vote_src { const float* p; int64_t item_stride; } dh_vote_src;   /* row k at p + k * item_stride, C dense floats */
+int dh_vote_products_f64(const dh_vote_src* srcs /* HOST table */, int nb, int C, const int32_t* seq /* device [n] */, int n,
+                         int nseq, double* acc /* device [nb, nseq, C], in/out */, int32_t* label_out /* device [nb, n] */,
+                         float* scores_out /* device [nb, n, C] or NULL */, void* stream);
+int dh_vote_products_host(const dh_vote_src* srcs, int nb, int C, const int32_t* seq /* [n] */, int n, int nseq,
+                          double* acc /* [nb, nseq, C], in/out */, int32_t* label_out /* [nb, n] */,
+                          float* scores_out /* [nb, n, C] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Stream-ordered runtime helpers (no torch types): graphs for launch-bound replay, events for timing.
  * ------------------------------------------------------------------------------------------------- */
 int dh_graph_begin_capture(void* stream);
