@@ -4,6 +4,7 @@ The product path has no CPU fallback: if the shared library is missing this modu
 Build it with `python -m deephar_amd.csrc.build` (or __graft_entry__.build()).
 """
 import ctypes as C
+import itertools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -136,6 +137,22 @@ def plan_record(lib, fn):
         return None
     assert n.value <= len(offs)
     return name.value.decode(), first.value, size.value, list(offs[:n.value])
+
+
+def sched_program(lib, entries, nstreams, npre):
+    """dh_sched_build_ops over a schedule table (engine/schedule.py: schedule_entries) as ([(kind, stream, arg, entry)],
+    number of events); a table the library refuses -- more than 4 streams, for one -- raises DeepharHipError."""
+    col = lambda vals: (i32 * (len(vals) + 1))(*vals)
+    waits = [w for e in entries for w in e[3]]
+    offs = list(itertools.accumulate([len(e[3]) for e in entries], initial=0))
+    args = (len(entries), col([-1 if e[0] is None else e[0] for e in entries]), col([e[1] for e in entries]),
+            col([e[2] for e in entries]), col(offs), col(waits), len(waits), nstreams, npre, sum(e[0] is not None for e in entries))
+    what = 'enqueue program of %d calls on %d streams (a plan has at most 4 streams)' % (len(entries), nstreams)
+    n, nev = C.c_int(), C.c_int()
+    check(lib.dh_sched_build_ops(*args, None, 0, C.byref(n), C.byref(nev)), what)
+    ops = (SchedOp * (n.value + 1))()
+    check(lib.dh_sched_build_ops(*args, ops, n.value, C.byref(n), C.byref(nev)), what)
+    return [(o.kind, o.stream, o.arg, o.entry) for o in ops[:n.value]], nev.value
 
 
 # name -> (restype, argtypes); every symbol include/deephar_hip.h declares

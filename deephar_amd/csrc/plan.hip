@@ -5,8 +5,8 @@
 // image.  The blob's format lives in plan_blob.h (GPU-free: the step-record table, the parser, the patch loop); this file
 // owns the allocations, patches the pointers once and replays the launches in order on the
 // caller's stream -- the same C-ABI entry points the Python executor calls, so the results are the same bits.  A version-5
-// blob carries the engine's multi-stream schedule: plan_sched.h (GPU-free) turns it into the enqueue program of
-// BoundPlan.launch_all, which dh_forward runs with the caller's stream as stream 0 and the plan's own side streams.  Every
+// blob carries the engine's multi-stream schedule: plan_sched.h (GPU-free) turns it into the enqueue program -- the one
+// BoundPlan.launch_all walks too -- which dh_forward runs with the caller's stream as stream 0 and the plan's own side streams.  Every
 // forward ends with ONE dh_pack_outputs_f32 launch (out_pack.hip) for all wanted outputs.
 // dh_frames_* / dh_forward_frames: a uint8 plan fed from full frames and boxes -- the crop program built on the device
 // (dh_crop_program_build_dev), ONE crop launch straight into the plan's uint8 input, then the forward with its input copy skipped.

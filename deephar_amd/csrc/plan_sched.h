@@ -1,9 +1,9 @@
 // The multi-stream schedule of a plan as a pure function: a table of schedule entries (one per bound call of the exporting
 // process: which blob step it launches, on which stream, whether it records an event, which earlier entries it waits for)
-// -> the enqueue program deephar_amd/engine/executor.py's BoundPlan.launch_all runs: LAUNCH / RECORD / WAIT ops in order.
-// No HIP header, no stream, no event: streams and events are small integers here.  dh_plan_create validates the schedule
-// section of a version-5 blob with this, dh_forward executes the op list, and the host tests ask it through
-// dh_sched_build_ops, so nobody restates the order.
+// -> the enqueue program: LAUNCH / RECORD / WAIT ops in order.  No HIP header, no stream, no event: streams and events are
+// small integers here.  Both executors run this one list, so nobody restates the order: dh_plan_create validates the schedule
+// section of a version-5 blob with it and dh_forward executes the ops; deephar_amd/engine/executor.py's BoundPlan.launch_all
+// asks dh_sched_build_ops for the program of its own calls and walks it (engine/schedule.py: run_program), as the host tests do.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from .. import _lib, frontend
-from . import binding, packing
+from . import binding, packing, schedule
 from .binding import grid_x, grid_depth      # noqa: F401  (their home is the binder; functional.py and the tests look here)
 
 SPLIT_CODES = packing.LAYOUT_CODES['standard']        # Plan.gemm_precision -> dh_conv_args.w_split (packing.LAYOUTS)
@@ -184,8 +184,8 @@ class BoundPlan:
         self.calls = []       # (fn, args tuple without stream, step)
         self._keep = []       # ctypes structs kept alive
         self.graph = None
-        # test hook (schedule stress tests): called as perturb(call index, step, stream of the step, [all streams]) right
-        # before every launch of launch_all -- e.g. to put dh_stream_spin_us delays on one stream
+        # test hook (schedule stress tests): perturb(call index, step, stream of the step, [all streams]), once per call in order,
+        # no later than the call's launch / record (schedule.run_program: before) -- e.g. dh_stream_spin_us delays on one stream
         self.perturb = None
         # uint8 frames: every model input gets a byte staging buffer; convolutions that read an input directly
         # normalise on load (dh_conv_args.x_u8), anything else is fed by a stand-alone normalisation launch
@@ -274,84 +274,50 @@ class BoundPlan:
         self.calls.append((getattr(self.lib, name), tuple(C.byref(st) for st in structs) + tuple(scalars), s))
 
     # ---- execution -----------------------------------------------------------------------------------------
+    _streams = _program = _sync = None      # made on first use: side streams | (ops, number of events) | the sync events by id
+
     def _side_streams(self, main_ptr=None):
-        """The extra HIP streams + sync events for the parallel branches of the plan.  [r06] The streams are the engine's
-        role streams other than the one this plan is launched on (shared_stream below: every stream the package creates costs one
-        of ROCm's four hardware queues, and a side stream that shares a queue with its plan's main stream is slow); only a plan
-        with more branches than those creates streams of its own."""
-        if getattr(self, '_streams', None) is None:
-            lib = self.lib
-            self._streams, self._events, self._join, self._fork, self._relay = [], {}, [], C.c_void_p(), {}
-            roles = [shared_stream(self.device, r) for r in ('head', 'comm', 'copy')]
+        """The extra HIP streams for the parallel branches of the plan.  [r06] They are the engine's role streams other than
+        the one this plan is launched on (shared_stream below: every stream the package creates costs one of ROCm's four hardware
+        queues, and a side stream that shares a queue with its plan's main stream is slow); only a plan with more branches than
+        those creates streams of its own."""
+        if self._streams is None:
+            roles = [shared_stream(self.device, r) for r in ('head', 'comm', 'copy')] if self.plan.nstreams > 1 else []
             spare = [st for st in roles if main_ptr is None or st.cuda_stream != main_ptr]
-            for k in range(self.plan.nstreams - 1):
-                st, ev = C.c_void_p(), C.c_void_p()
-                if k < len(spare):
-                    st = C.c_void_p(spare[k].cuda_stream)
-                else:
-                    _lib.check(lib.dh_stream_create(C.byref(st)), 'stream create')
-                _lib.check(lib.dh_event_create_sync(C.byref(ev)), 'event create')
-                self._streams.append(st)
-                self._join.append(ev)
-            _lib.check(lib.dh_event_create_sync(C.byref(self._fork)), 'event create')
-            for i, (_, _, step) in enumerate(self.calls):
-                if step.record:
-                    ev = C.c_void_p()
-                    _lib.check(lib.dh_event_create_sync(C.byref(ev)), 'event create')
-                    self._events[i] = ev
+            self._streams = [C.c_void_p(st.cuda_stream) for st in spare[:self.plan.nstreams - 1]]
+            while len(self._streams) < self.plan.nstreams - 1:
+                self._streams.append(C.c_void_p())
+                _lib.check(self.lib.dh_stream_create(C.byref(self._streams[-1])), 'stream create')
         return self._streams
 
+    def program(self):
+        """-> (ops, number of events) of `calls`, from the scheduler dh_forward runs too (csrc/plan_sched.h); built on first use"""
+        if self._program is None:
+            entries = schedule.schedule_entries([c[2] for c in self.calls], self.npre, self.noop_calls)
+            self._program = _lib.sched_program(self.lib, entries, self.plan.nstreams, self.npre)
+        return self._program
+
     def launch_all(self, stream_ptr):
-        """Enqueue the whole plan.  With one stream: plain in-order launches.  With several: steps go to
-        their scheduled stream, cross-stream dependencies become event waits, side streams fork from / join
+        """Enqueue the whole plan: walk program() with `stream_ptr` as stream 0.  One stream: the launches in order.  Several:
+        steps go to their scheduled stream, cross-stream dependencies are event waits, and the side streams fork from / join
         back into `stream_ptr` (so the sequence is capturable into one hipGraph)."""
-        lib = self.lib
-        if self.plan.nstreams <= 1:
-            for i, (fn, args, step) in enumerate(self.calls):
-                if self.perturb is not None:
-                    self.perturb(i, step, stream_ptr, [stream_ptr])
-                rc = fn(*args, stream_ptr)
-                if rc != 0:
-                    _lib.check(rc, 'step %s (%s)' % (step.kind, step.name))
-            return
-        side = self._side_streams(stream_ptr)
-        ptrs = [stream_ptr] + [st for st in side]
-        for fn, args, step in self.calls[:self.npre]:          # input staging runs before the fork
-            _lib.check(fn(*args, stream_ptr), step.kind)
-        _lib.check(lib.dh_event_record(self._fork, stream_ptr), 'fork')
-        for st in side:
-            _lib.check(lib.dh_stream_wait_event(st, self._fork), 'fork wait')
-        for i, (fn, args, step) in enumerate(self.calls):
-            if i < self.npre:
-                continue
-            sp = ptrs[step.stream]
-            for w in step.wait:
-                ev = self._events[w + self.npre]
-                src = self.calls[w + self.npre][2].stream
-                if step.stream != 0 and src > step.stream:
-                    # ROCm 7.2 stream capture segfaults (hipStreamEndCapture) once two SIDE streams have waited on
-                    # each other's events in both directions (tools/micro/capture_pattern.hip).  A lower-numbered
-                    # side stream therefore never waits on a higher-numbered one directly: the origin stream waits
-                    # and re-publishes the dependency.
-                    key = (i, w)
-                    if key not in self._relay:
-                        r = C.c_void_p()
-                        _lib.check(lib.dh_event_create_sync(C.byref(r)), 'event create')
-                        self._relay[key] = r
-                    _lib.check(lib.dh_stream_wait_event(stream_ptr, ev), 'relay wait')
-                    _lib.check(lib.dh_event_record(self._relay[key], stream_ptr), 'relay record')
-                    ev = self._relay[key]
-                _lib.check(lib.dh_stream_wait_event(sp, ev), 'dependency wait')
-            if self.perturb is not None:
-                self.perturb(i, step, sp, ptrs)
-            rc = fn(*args, sp)
+        lib, calls, (ops, nevents) = self.lib, self.calls, self.program()
+        ptrs = [stream_ptr] + self._side_streams(stream_ptr)
+        if self._sync is None and len(ptrs) > 1:
+            self._sync = [C.c_void_p() for _ in range(nevents)]
+            for ev in self._sync:
+                _lib.check(lib.dh_event_create_sync(C.byref(ev)), 'event create')
+        sync = self._sync
+        def launch(i, s):
+            fn, args, step = calls[i]                  # (looked up now: bench.py assigns into `calls` after binding)
+            rc = fn(*args, ptrs[s])
             if rc != 0:
                 _lib.check(rc, 'step %s (%s)' % (step.kind, step.name))
-            if step.record:
-                _lib.check(lib.dh_event_record(self._events[i], sp), 'event record')
-        for st, ev in zip(side, self._join):
-            _lib.check(lib.dh_event_record(ev, st), 'join record')
-            _lib.check(lib.dh_stream_wait_event(stream_ptr, ev), 'join wait')
+
+        record = lambda ev, s: _lib.check(lib.dh_event_record(sync[ev], ptrs[s]), 'event record')
+        wait = lambda ev, s: _lib.check(lib.dh_stream_wait_event(ptrs[s], sync[ev]), 'event wait')
+        before = self.perturb and (lambda i: self.perturb(i, calls[i][2], ptrs[calls[i][2].stream], ptrs))
+        schedule.run_program(ops, launch, record, wait, before, len(calls))
 
     # ---- grouped launches (latency regime) ------------------------------------------------------------------------
     GROUP_MAX_ROWS = 8192           # conv rows (pixels of the bound batch) up to which a pair is merged
@@ -395,6 +361,7 @@ class BoundPlan:
         self._pair_skinny_convs(stream_ptr)
         if self.grouped or self.paired:
             self._drop_graph()
+            self._program = None                       # noop_calls changed
         return self.grouped
 
     def _absorb(self, i, k, fn):

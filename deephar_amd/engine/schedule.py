@@ -351,3 +351,32 @@ def finalize(plan, nstreams=1, policy='list'):
     plan.nstreams = max(stream) + 1 if n else 1
     allocate(plan, reach)
     return plan
+
+
+def schedule_entries(steps, npre=0, noop=()):
+    """-> [(blob step index or None, stream, records, [entry indices it waits for])], one per bound call: the table of
+    csrc/plan_sched.h, which the exporter writes (serialize.pack_schedule) and BoundPlan.program builds its ops from.  steps:
+    the Step of every call in launch order (BoundPlan.calls; a Plan's steps for a plan that is not bound: npre = 0); npre: the
+    leading input-staging calls; noop: calls absorbed into an earlier launch (BoundPlan.noop_calls).  Step.wait holds
+    plan-step indices: call index = plan-step index + npre."""
+    idx = {i: k for k, i in enumerate(i for i in range(len(steps)) if i not in noop)}     # launching call -> blob step
+    return [(idx.get(i), int(st.stream), bool(st.record), [int(w) + npre for w in st.wait]) for i, st in enumerate(steps)]
+
+
+def run_program(ops, launch, record, wait, before=None, nentries=0):
+    """Walk an enqueue program (_lib.sched_program: (kind, stream, arg, entry) ops of dh_sched_build_ops) in order:
+    launch(entry, stream) | record(event id, stream) | wait(event id, stream).  before(i), if given, is called once for every
+    entry i < nentries in increasing order, no later than the first op of entry i.  An entry without any op (absorbed, no
+    record, no wait) gets its call with the next entry that has one; behind the last of those, in front of the join."""
+    call = (launch, record, wait)                   # by dh_sched_op.kind: DH_SCHED_LAUNCH 0, _RECORD 1, _WAIT 2
+    nxt, last = 0, max((k for k, op in enumerate(ops) if op[3] >= 0), default=-1) if before is not None else -1
+    for k, (kind, stream, arg, entry) in enumerate(ops):
+        if before is not None:
+            upto = nentries if k > last else entry + 1
+            while nxt < upto:
+                before(nxt)
+                nxt += 1
+        call[kind](arg if kind else entry, stream)
+    while before is not None and nxt < nentries:    # (one stream, or nothing behind the last entry's ops)
+        before(nxt)
+        nxt += 1

@@ -31,9 +31,9 @@ with a schedule section between the steps and the weight image, the engine's mul
                paired launch; it keeps its entry so that it still records its event at its own place)
                | u32 stream | u32 flags (bit 0: an event is recorded behind it) | u32 #waits of this entry
              waits   u32 entry index per wait, entry by entry: an EARLIER entry on another stream that records
-The library turns the table into the enqueue program of BoundPlan.launch_all (csrc/plan_sched.h: fork, per-entry waits /
-launch / record, the relay rule, join) and refuses a table that breaks one of the rules above, more than 4 streams, or sizes
-that do not add up.
+The table is schedule.schedule_entries of the bound calls, the one BoundPlan.launch_all runs from.  The library turns it into
+the enqueue program both executors run (csrc/plan_sched.h: fork, per-entry waits / launch / record, the relay rule, join) and
+refuses a table that breaks one of the rules above, more than 4 streams, or sizes that do not add up.
 
 Clip container (little endian), version 1: a frame-sharded clip model (parallel.ShardedClipModel) as ONE file for
 dh_clip_inspect / dh_clip_create / dh_clip_forward -- the two stage plans and the cut table between them:
@@ -52,6 +52,7 @@ import struct
 import numpy as np
 
 from .. import _lib
+from .schedule import schedule_entries      # (its home is the scheduler: the table BoundPlan runs from)
 
 MAGIC, VERSION = b'DHPL', 2
 FUNCTIONS = ['dh_conv2d_f32', 'dh_dwconv2d_f32', 'dh_pool2d_f32', 'dh_upsample2x_add_f32', 'dh_eltwise_f32',
@@ -176,20 +177,6 @@ def blob_version(function_ids):
 
 SCHEDULE_VERSION = 5            # blob version of a plan written with its multi-stream schedule
 NO_LAUNCH = 0xffffffff          # schedule entry whose work moved into an earlier grouped / paired launch
-
-
-def schedule_entries(steps, npre=0, noop=()):
-    """-> [(blob step index or None, stream, records, [entry indices it waits for])], one per bound call.  steps: the Step of
-    every call in launch order (BoundPlan.calls; a Plan's steps for a plan that is not bound: npre = 0); npre: the leading
-    input-staging calls; noop: indices of calls absorbed into an earlier launch (BoundPlan.noop_calls).  Step.wait holds
-    plan-step indices: call index = plan-step index + npre, as in BoundPlan.launch_all.  No device needed."""
-    entries, launched = [], 0
-    for i, st in enumerate(steps):
-        idx = None
-        if i not in noop:
-            idx, launched = launched, launched + 1
-        entries.append((idx, int(st.stream), bool(st.record), [int(w) + npre for w in st.wait]))
-    return entries
 
 
 def pack_schedule(entries, nstreams, npre=0):

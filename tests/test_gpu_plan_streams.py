@@ -162,6 +162,16 @@ def _exports_reproduce_one_stream_predict(lib, cuda, tmp_path, case, m):
     v5 = _export(m, n, tmp_path, 'multi.dhplan', multi_stream=True)
     plain = _export(m, n, tmp_path, 'plain.dhplan')
     assert _version(v5) == 5 and _version(plain) <= 4 and len(v5) > len(plain)
+    # both executors run the same list: the program of the exported blob is the bound plan's own
+    from deephar_amd import _lib
+    info = _lib.PlanInfo()
+    assert lib.dh_plan_inspect(v5, len(v5), C.byref(info)) == 0
+    ops, nevents = m.executor.bound[n].program()
+    assert (info.nstreams, info.num_ops, info.num_events) == (m.plan.nstreams, len(ops), nevents)
+    for graph in (False, True):                                     # ... and what Python enqueues from it returns the same bits
+        m.executor.use_graph = graph
+        got = m.predict(case.x, batch_size=n)
+        _same(got if isinstance(got, list) else [got], case.ref)
     for blob, streams in [(v5, m.plan.nstreams), (plain, 1)]:
         plan = _create(lib, blob)
         try:

@@ -237,7 +237,7 @@ def test_version_1_and_version_5_forms(hip_lib):
     plan = PS.get_plan('reception', 2, 'list')
     section = S.schedule_section(plan.steps, plan.nstreams, multi_stream=True)
     blob, want, _ = host_blob(plan, 1, section)
-    rc, ops, nev = PS.build_ops(hip_lib, S.schedule_entries(plan.steps), 2, 0)
+    rc, ops, nev = PS.build_ops(hip_lib, PS.schedule.schedule_entries(plan.steps), 2, 0)
     rc5, info = inspect(hip_lib, blob)
     assert rc == 0 and rc5 == 0 and want['version'] == 5
     check_info(info, dict(want, nstreams=2, num_ops=len(ops), num_events=nev))

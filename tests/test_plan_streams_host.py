@@ -5,8 +5,10 @@ slicing; and the export keyword leaving every single-stream blob as it was.  Not
 exact.  tools/sched_sweep.cpp runs random tables through the same two headers as a stand-alone program for a sanitizer build."""
 import ctypes as C
 import functools
+import hashlib
 import inspect
 import struct
+import types
 
 import numpy as np
 import pytest
@@ -147,7 +149,7 @@ def test_enqueue_program_keeps_the_plans_happens_before(kind, streams, policy, h
     section = serialize.schedule_section(plan.steps, plan.nstreams, multi_stream=True)
     ns, npre, entries = unpack_section(section)
     assert (ns, npre, len(entries)) == (plan.nstreams, 0, len(plan.steps))
-    assert entries == serialize.schedule_entries(plan.steps)
+    assert entries == schedule.schedule_entries(plan.steps)
     for j, (e, s) in enumerate(zip(entries, plan.steps)):
         assert e == (j, s.stream, bool(s.record), list(s.wait))
     rc, ops, nev = build_ops(hip_lib, entries, ns, npre)
@@ -185,11 +187,17 @@ def test_hand_made_table_needs_a_relay(hip_lib):
     assert rc == 0 and ops == [(LAUNCH, 0, i, i) for i in range(4)] and nev == 1
 
 
+ABSORBED = [(0, 0, False, []), (1, 0, True, []), (2, 2, True, [1]), (3, 1, True, [2]), (None, 1, True, []), (4, 0, False, [4]),
+            (5, 2, False, [3])]
+# ... and with entries that have no op at all (absorbed, no record, no wait): in the middle (2) and behind everything (8)
+OPLESS = [(0, 0, False, []), (1, 0, True, []), (None, 0, False, []), (2, 2, True, [1]), (3, 1, True, [3]), (None, 1, True, []),
+          (4, 0, False, [5]), (5, 2, False, [4]), (None, 2, False, [])]
+
+
 def test_absorbed_entry_still_records_at_its_place(hip_lib):
     """(f) entry 4 (records, no waits) absorbed into an earlier launch of its stream: no LAUNCH, its RECORD stays behind the
     absorbing launch on the same stream, and the waiter is still ordered behind that launch."""
-    table = [(0, 0, False, []), (1, 0, True, []), (2, 2, True, [1]), (3, 1, True, [2]), (None, 1, True, []), (4, 0, False, [4]),
-             (5, 2, False, [3])]
+    table = ABSORBED
     rc, ops, nev = build_ops(hip_lib, table, 3, 1)
     assert rc == 0
     launch_pos, after, relays = check_program(ops, nev, table, 3, 1)
@@ -198,6 +206,167 @@ def test_absorbed_entry_still_records_at_its_place(hip_lib):
     assert len(rec) == 1 and ops[rec[0]][1] == 1 and rec[0] > launch_pos[3]
     assert not any(o[0] == LAUNCH and o[1] == 1 for o in ops[launch_pos[3] + 1:rec[0]])
     assert after[launch_pos[3]] >> 5 & 1                           # entry 5 waits for the event: ordered behind the absorbing launch
+
+
+# ---- what Python enqueues: the walker, and BoundPlan.launch_all over it ----------------------------------------------------------
+
+def walk(ops, nentries):
+    """schedule.run_program over `ops` with recording callbacks -> the log: ops as the walker handed them out, ('before', i)"""
+    log = []
+    schedule.run_program(ops, lambda e, s: log.append((LAUNCH, s, e)), lambda ev, s: log.append((RECORD, s, ev)),
+                         lambda ev, s: log.append((WAIT, s, ev)), lambda i: log.append(('before', i)), nentries)
+    return log
+
+
+@pytest.mark.parametrize('case', PLANS + ['hand', 'absorbed', 'opless', 'one stream'], ids=str)
+def test_walker_hands_out_the_program_one_for_one(case, hip_lib):
+    if isinstance(case, tuple):
+        plan = get_plan(*case)
+        entries, ns, npre = schedule.schedule_entries(plan.steps), plan.nstreams, 0
+    else:
+        entries, ns, npre = {'hand': (HAND, 3, 1), 'absorbed': (ABSORBED, 3, 1), 'opless': (OPLESS, 3, 1),
+                             'one stream': ([(0, 0, False, []), (None, 0, False, []), (1, 0, False, []), (None, 0, False, [])], 1, 1)}[case]
+    ops, nev = _lib.sched_program(hip_lib, entries, ns, npre)
+    assert (0, ops, nev) == build_ops(hip_lib, entries, ns, npre)
+    log = walk(ops, len(entries))
+    # same kind, stream, event id / entry, in order (a LAUNCH is handed out by entry: the step is the caller's to look up)
+    assert [o for o in log if o[0] != 'before'] == [(k, s, e if k == LAUNCH else a) for k, s, a, e in ops]
+    # `before`: once per entry, in increasing order, no later than the entry's first LAUNCH / RECORD -- and in front of the join
+    assert [o[1] for o in log if o[0] == 'before'] == list(range(len(entries)))
+    seen, at = set(), 0
+    for o in log:
+        if o[0] == 'before':
+            seen.add(o[1])
+            continue
+        kind, stream, arg, entry = ops[at]
+        at += 1
+        assert entry < 0 or kind == WAIT or entry in seen, ('op of an entry in front of its hook', at - 1, entry)
+        if at > len(ops) - 2 * (ns - 1):
+            assert len(seen) == len(entries), 'a hook behind the join'
+    opless = [i for i, e in enumerate(entries) if e[0] is None and not e[2] and not e[3]]
+    assert not any(o[3] in opless for o in ops) and (case not in ('opless', 'one stream') or len(opless) == 2)
+    # without the hook nothing else changes
+    plain = []
+    schedule.run_program(ops, lambda e, s: plain.append((LAUNCH, s, e)), lambda ev, s: plain.append((RECORD, s, ev)),
+                         lambda ev, s: plain.append((WAIT, s, ev)))
+    assert plain == [o for o in log if o[0] != 'before']
+
+
+def test_more_than_four_streams_are_refused_by_name(hip_lib):
+    table = [(0, 0, True, [])] + [(k, k, False, [0]) for k in range(1, 5)]
+    assert len(_lib.sched_program(hip_lib, table[:4], 4, 0)[0]) == 4 + 4 + 3 + 1 + 6
+    with pytest.raises(_lib.DeepharHipError, match='at most 4 streams'):
+        _lib.sched_program(hip_lib, table, 5, 0)
+
+
+MAIN_STREAM, ROLE_STREAMS = 0x1000, {'head': 0x2000, 'comm': 0x3000, 'copy': 0x4000}
+
+
+class RecordingLib:
+    """stand-in for BoundPlan.lib without a device: stream and event calls are written down, the scheduler is the library's"""
+
+    def __init__(self, lib):
+        self.lib, self.trace, self.handles = lib, [], 0
+
+    def __getattr__(self, name):
+        return getattr(self.lib, name)
+
+    def _create(self, ref):
+        self.handles += 1
+        ref._obj.value = 0x10000 + 16 * self.handles
+        return 0
+
+    dh_event_create_sync = dh_stream_create = _create
+
+    def dh_event_record(self, ev, stream):
+        self.trace.append((RECORD, getattr(stream, 'value', stream), ev.value))
+        return 0
+
+    def dh_stream_wait_event(self, stream, ev):
+        self.trace.append((WAIT, getattr(stream, 'value', stream), ev.value))
+        return 0
+
+
+def enqueue_trace(executor, lib, plan, npre=0, absorbed=()):
+    """What `executor`.BoundPlan.launch_all enqueues for `plan` behind `npre` staging calls, the calls in `absorbed` being no-ops,
+    as [(kind, stream index, entry | event)] with events numbered by their first RECORD.  No device: the BoundPlan is made
+    without __init__, its library is a RecordingLib and the role streams are numbers."""
+    rec = RecordingLib(lib)
+    bp = executor.BoundPlan.__new__(executor.BoundPlan)
+    steps = [executor._InputStep(None) for _ in range(npre)] + list(plan.steps)
+    bp.lib, bp.plan, bp.npre, bp.device, bp.perturb, bp.graph, bp.noop_calls = rec, plan, npre, None, None, None, set(absorbed)
+    bp.calls = [(executor._noop_launch, (), st) if i in bp.noop_calls else
+                ((lambda stream, i=i: rec.trace.append((LAUNCH, getattr(stream, 'value', stream), i)) or 0), (), st)
+                for i, st in enumerate(steps)]
+    shared, executor.shared_stream = executor.shared_stream, lambda device, role: types.SimpleNamespace(cuda_stream=ROLE_STREAMS[role])
+    try:
+        bp.launch_all(MAIN_STREAM)
+    finally:
+        executor.shared_stream = shared
+    streams = [MAIN_STREAM] + [st.value for st in getattr(bp, '_streams', None) or []]
+    assert streams[1:] == list(ROLE_STREAMS.values())[:plan.nstreams - 1]      # the role streams first, in their order
+    return canonical(rec.trace, streams.index)
+
+
+def canonical(trace, stream_index=int):
+    events, out = {}, []
+    for kind, stream, arg in trace:
+        if kind == RECORD:
+            events.setdefault(arg, len(events))
+        out.append((kind, stream_index(stream), arg if kind == LAUNCH else events[arg]))
+    return out
+
+
+# sha256 of repr(enqueue_trace(...)) and (ops, waits, relays), recorded from the last commit whose launch_all had loops of its own
+# (fork / wait / relay / launch / record / join, and a second loop for one stream) instead of walking the library's program:
+# that BoundPlan was driven by enqueue_trace exactly as here, and the order of stream and event calls has not moved since.
+# Variant 'bare': the plan's steps; 'staged+absorbed': one staging call in front and call 1 + len(steps) // 2 absorbed.
+RECORDED_TRACES = {
+    ('spnet', 2, 'tail', 'bare'): ('ccf16f0cfd15caac507d95e86952beb58310429590f9b7131d043718e1d44e24', (173, 8, 0)),
+    ('spnet', 2, 'tail', 'staged+absorbed'): ('6caec2e8da00231071019da6b35c083cd836c3655dbfeeaa63319f2e7e8fe6bd', (173, 8, 0)),
+    ('spnet', 3, 'tail', 'bare'): ('15987810ff995705635021a564e88c2ffb74e2c578ad861799bb16cd54f1f344', (186, 15, 0)),
+    ('spnet', 3, 'tail', 'staged+absorbed'): ('7eecdac31253b8fa102f622fe8e400916abf3145a0f85ec3080c6682c5943edd', (186, 15, 0)),
+    ('spnet', 2, 'list', 'bare'): ('4539a13011445f161cbe8cab3903870cc615c7ee2b8c7320da533e57ec86b2b2', (243, 43, 0)),
+    ('spnet', 2, 'list', 'staged+absorbed'): ('cd125bba18a81ea8559b8bfadff9f3412a71fee9246f8634e4f95934535923f5', (243, 43, 0)),
+    ('reception', 2, 'list', 'bare'): ('902aa73d94456d0a1a1a85b974d7ecddb06d3a29382911de453beec2a42d7bd2', (99, 21, 0)),
+    ('reception', 2, 'list', 'staged+absorbed'): ('668bb8c6bc76ff33bca5eb9fb1ed204cdb8257c029f5a2d3cbe1fa9f269896e9', (99, 21, 0)),
+    ('reception', 3, 'list', 'bare'): ('d45d20e60166b986eb0137ce0c450e3e30779e44b3e7c22e4d6ce152b7f1a188', (111, 28, 4)),
+    ('reception', 3, 'list', 'staged+absorbed'): ('308b6f523991fcb98d2bd237c8e8061792346121ee4d35e3fbdde30c593b69de', (111, 28, 4)),
+    ('spnet', 1, 'tail', 'bare'): ('8b40093e16fc5325ea8d5a38939b41e77592042fc6fab1fccc3d16d4a784879c', (157, 0, 0)),
+    ('spnet', 1, 'tail', 'staged+absorbed'): ('daa305846a546d5a0c484ffc6fc721ade9f6a832e4e673ad9ab950e0af0a7d2a', (157, 0, 0)),
+    ('reception', 1, 'list', 'bare'): ('528dc9914e12bc9d3990e57d1dfd723fa56dd9c02a6584e45b62642a14857684', (57, 0, 0)),
+    ('reception', 1, 'list', 'staged+absorbed'): ('8d250f0968a230427c6129eaf4ec051c16d5ba02bbd99f156fde4de115035fec', (57, 0, 0)),
+}
+
+
+def trace_case(kind, streams, policy, variant, hip_lib):
+    from deephar_amd.engine import executor
+    plan = get_plan(kind, streams, policy)
+    assert plan.nstreams == streams
+    npre, absorbed = (0, ()) if variant == 'bare' else (1, (1 + len(plan.steps) // 2,))
+    trace = enqueue_trace(executor, hip_lib, plan, npre, absorbed)
+    # what was enqueued is the library's program, one for one
+    entries = schedule.schedule_entries([executor._InputStep(None)] * npre + list(plan.steps), npre, absorbed)
+    ops, nev = _lib.sched_program(hip_lib, entries, streams, npre)
+    assert trace == canonical([(k, s, e if k == LAUNCH else a) for k, s, a, e in ops])
+    nrec = sum(1 for e in entries if e[2])
+    nevents = len({o[2] for o in trace if o[0] == RECORD})          # fork + joins + recording entries + relays
+    counts = (len(trace), sum(1 for o in trace if o[0] == WAIT), nevents - nrec - (streams if streams > 1 else 0))
+    return hashlib.sha256(repr(trace).encode()).hexdigest(), counts
+
+
+@pytest.mark.parametrize('variant', ['bare', 'staged+absorbed'])
+@pytest.mark.parametrize('kind,streams,policy', PLANS)
+def test_launch_all_enqueues_the_recorded_order_multi_stream(kind, streams, policy, variant, hip_lib):
+    assert trace_case(kind, streams, policy, variant, hip_lib) == RECORDED_TRACES[kind, streams, policy, variant]
+
+
+@pytest.mark.parametrize('variant', ['bare', 'staged+absorbed'])
+@pytest.mark.parametrize('kind,streams,policy', [('spnet', 1, 'tail'), ('reception', 1, 'list')])
+def test_launch_all_enqueues_the_recorded_order_one_stream(kind, streams, policy, variant, hip_lib):
+    digest, counts = trace_case(kind, streams, policy, variant, hip_lib)
+    assert (digest, counts) == RECORDED_TRACES[kind, streams, policy, variant]
+    assert counts == (len(get_plan(kind, streams, policy).steps), 0, 0)          # the launches (one staged, one absorbed), no event
 
 
 def test_malformed_tables_are_refused(hip_lib):
@@ -344,7 +513,7 @@ def test_single_stream_exports_are_unchanged_by_the_keyword():
         def __init__(self, stream, record, wait):
             self.stream, self.record, self.wait = stream, record, wait
     steps = [S(0, False, ()), S(0, True, []), S(1, False, [0]), S(1, True, []), S(0, False, [2])]
-    assert serialize.schedule_entries(steps, npre=1, noop={3}) == \
+    assert schedule.schedule_entries(steps, npre=1, noop={3}) == \
         [(0, 0, False, []), (1, 0, True, []), (2, 1, False, [1]), (None, 1, True, []), (3, 0, False, [3])]
-    assert unpack_section(serialize.pack_schedule(serialize.schedule_entries(steps, 1, {3}), 2, 1))[2] == \
-        serialize.schedule_entries(steps, 1, {3})
+    assert unpack_section(serialize.pack_schedule(schedule.schedule_entries(steps, 1, {3}), 2, 1))[2] == \
+        schedule.schedule_entries(steps, 1, {3})

@@ -34,32 +34,29 @@ lib = bp.lib
 main = ex.stream_ptr
 for _ in range(3): bp.launch_all(main)
 torch.cuda.synchronize()
-side = bp._side_streams()
-ptrs = [main] + list(side)
-def ev():
-    e = C.c_void_p(); _lib.check(lib.dh_event_create(C.byref(e))); return e
+ptrs = [main] + list(bp._side_streams())
+def ev(sync=False):
+    e = C.c_void_p(); _lib.check((lib.dh_event_create_sync if sync else lib.dh_event_create)(C.byref(e))); return e
 n = len(bp.calls)
 E0 = ev(); starts = [ev() for _ in range(n)]; ends = [ev() for _ in range(n)]
-# replica of BoundPlan.launch_all with timing events around every step on its own stream
+# BoundPlan.launch_all's walk of the plan's enqueue program, with timing events around every launch on its own stream
+ops, nevents = bp.program()
+sync = [ev(True) for _ in range(nevents)]
+def launch(i, s):
+    fn, args, step = bp.calls[i]
+    _lib.check(lib.dh_event_record(starts[i], ptrs[s]))
+    _lib.check(fn(*args, ptrs[s]))
+    _lib.check(lib.dh_event_record(ends[i], ptrs[s]))
 _lib.check(lib.dh_event_record(E0, main))
-_lib.check(lib.dh_event_record(bp._fork, main))
-for st in side: _lib.check(lib.dh_stream_wait_event(st, bp._fork))
-for i, (fn, args, step) in enumerate(bp.calls):
-    sp = ptrs[step.stream]
-    for w in step.wait:
-        e = bp._events[w + bp.npre]
-        _lib.check(lib.dh_stream_wait_event(sp, e))
-    _lib.check(lib.dh_event_record(starts[i], sp))
-    _lib.check(fn(*args, sp))
-    _lib.check(lib.dh_event_record(ends[i], sp))
-    if step.record: _lib.check(lib.dh_event_record(bp._events[i], sp))
-for st, e in zip(side, bp._join):
-    _lib.check(lib.dh_event_record(e, st)); _lib.check(lib.dh_stream_wait_event(main, e))
+schedule.run_program(ops, launch, lambda e, s: _lib.check(lib.dh_event_record(sync[e], ptrs[s])),
+                     lambda e, s: _lib.check(lib.dh_stream_wait_event(ptrs[s], sync[e])))
 torch.cuda.synchronize()
 def t(e):
     ms = C.c_float(); _lib.check(lib.dh_event_elapsed_ms(E0, e, C.byref(ms))); return ms.value * 1e3
 rows = []
 for i, (fn, args, step) in enumerate(bp.calls):
+    if i in bp.noop_calls:                        # (its work runs inside an earlier launch: nothing was timed)
+        continue
     v = next(iter(step.outs.values()), None) if step.outs else None
     rows.append((t(starts[i]), t(ends[i]), step.stream, step.kind, tuple(v.shape[-3:]) if v is not None else ()))
 print('policy %s: forward %.1f us, sum of step times %.1f us' % (policy, max(r[1] for r in rows), sum(r[1] - r[0] for r in rows)))
