@@ -82,10 +82,11 @@ struct EpiPrefetch {
     return (epi_vec & 2) != 0 && m0 + WM * TM * 32 <= M && n0 + WN * TN * 32 <= p.Cout;
   }
 
-  template <int WM, int WN>
+  // DIRECT = false: the caller finishes its direct tiles itself, slice by slice (EpiDirect), and only comes here for the rest
+  template <int WM, int WN, bool DIRECT = true>
   __device__ __forceinline__ void issue(const ConvArgs& p, int m0, int n0, int M, int epi_vec) {
     if constexpr (kEnabled) {
-      if (direct_tile<WM, WN>(p, m0, n0, M, epi_vec)) {
+      if (DIRECT && direct_tile<WM, WN>(p, m0, n0, M, epi_vec)) {
         // accumulator layout: register r of lane (li, lh) is row (r & 3) + 8 * (r >> 2) + 4 * lh, column li of the tile
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int wm = wave / WN, wn = wave % WN;
@@ -127,6 +128,114 @@ struct EpiPrefetch {
   }
 };
 
+// The direct epilogue one 32 x 32 column tile (a SLICE) at a time.  Register r of lane (li, lh) is row (r & 3) + 8 * (r >> 2) +
+// 4 * lh, column li of the tile: a store instruction writes two 128-byte row segments, BN scale / shift are one value per
+// lane, the row step is a scalar offset -- no vector-ALU address arithmetic.  A kernel whose wave holds one row block
+// (TM == 1) finishes slice j while the matrix pipe works on slice j + 1 (gemm1x1_body.h); what a slice reads besides
+// its accumulators travels in an EpiSlice, requested one slice ahead.
+struct EpiSlice {
+  float r1[16];     // res1 at the lane's 16 elements
+  float r2[8];      // res2_down: registers r and r ^ 1 of a lane read the same half-resolution pixel
+  float sc, sh;     // BN scale / shift of the lane's column
+};
+
+using rsrc_t = decltype(__builtin_amdgcn_make_buffer_rsrc((float*)nullptr, (short)0, 0, 0));
+
+// R2: the launch may carry a second residual at HALF resolution (res2_down; the launcher only sets the direct flag on
+// maps of 2^a x 2^b >= 32 pixels with OW >= 8): the wave's 32 pixels start at an even image row, so with
+// t = (r & 3) + 8 * (r >> 2) + 4 * lh the source pixel splits into a wave-uniform part per register and 2 * lh * ldr2 per lane.
+template <int WM, int WN, int TN, bool R2 = true>
+struct EpiDirect {
+  rsrc_t rs_y, rs_1, rs_2;
+  int vo_y, vo_1, vo_2, ncol;          // per-lane byte offsets into y / res1 / res2, the lane's column in slice 0
+  int fr, oh0, ow0, ow_sh;             // (wave-uniform) frame and pixel of the wave's first row
+
+  __device__ __forceinline__ EpiDirect(const ConvArgs& p, int m0, int n0, int M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const int li = lane & 31, lh = lane >> 5;
+    rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)(((unsigned)(M - 1) * p.ldy + (unsigned)p.Cout) * 4u), 0x00020000);
+    rs_1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res1), 0,
+                                             (int)(((unsigned)(M - 1) * p.ldr1 + (unsigned)p.Cout) * 4u), 0x00020000);
+    rs_2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res2), 0,
+                                             (int)(((unsigned)((M >> 2) - 1) * p.ldr2 + (unsigned)p.Cout) * 4u), 0x00020000);
+    ncol = n0 + wn * TN * 32 + li;
+    const int row0 = m0 + wm * 32 + 4 * lh;
+    vo_y = (row0 * p.ldy + ncol) * 4;
+    vo_1 = (row0 * p.ldr1 + ncol) * 4;
+    vo_2 = (2 * lh * p.ldr2 + ncol) * 4;
+    const int ohw = p.OH * p.OW;
+    const int mb = __builtin_amdgcn_readfirstlane(m0 + wm * 32);
+    const int pos = mb & (ohw - 1);
+    ow_sh = __ffs(p.OW) - 1;
+    fr = mb >> (__ffs(ohw) - 1);
+    oh0 = pos >> ow_sh;
+    ow0 = pos & (p.OW - 1);
+  }
+
+  __device__ __forceinline__ void request_bn(const ConvArgs& p, int j, EpiSlice& s) const {
+    if (p.post_scale != nullptr) {
+      s.sc = p.post_scale[ncol + j * 32];
+      s.sh = p.post_shift[ncol + j * 32];
+    }
+  }
+  __device__ __forceinline__ void request_res1(const ConvArgs& p, int j, EpiSlice& s) const {
+    if (p.res1 != nullptr) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s.r1[r] = buf_ld1_stream(rs_1, vo_1, (((r & 3) + 8 * (r >> 2)) * p.ldr1 + j * 32) * 4);
+    }
+  }
+  __device__ __forceinline__ void request_res2(const ConvArgs& p, int j, EpiSlice& s) const {
+    if (R2 && p.res2 != nullptr) {                       // (uniform) direct tiles carry res2 only as res2_down
+#pragma unroll
+      for (int h = 0; h < 8; ++h) {
+        const int tr = 2 * (h & 1) + 8 * (h >> 1);        // rows (2h, 2h + 1) -> registers r = 2h, 2h + 1
+        const int oh = oh0 + (tr >> ow_sh), ow = ow0 + (tr & (p.OW - 1));
+        const int src = (fr * (p.OH >> 1) + (oh >> 1)) * (p.OW >> 1) + (ow >> 1);
+        s.r2[h] = buf_ld1_stream(rs_2, vo_2, (src * p.ldr2 + j * 32) * 4);
+      }
+    }
+  }
+  // everything slice j reads besides its accumulators
+  __device__ __forceinline__ void request(const ConvArgs& p, int j, EpiSlice& s) const {
+    request_bn(p, j, s);
+    request_res1(p, j, s);
+    request_res2(p, j, s);
+  }
+
+  // out = relu?( acc * sc + sh + res1 + res2 ) of slice j, stored.  The launch-uniform flags are scalar branches around
+  // whole 16-element loops (a select per element would be paid beside the MFMAs like any other VALU); an absent term is
+  // skipped, not added as zero.
+  __device__ __forceinline__ void finish(const ConvArgs& p, int j, const f32x16& acc, const EpiSlice& s) const {
+    float t[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = acc[r];
+    if (p.post_scale != nullptr) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t[r] = t[r] * s.sc + s.sh;
+    }
+    if (p.res1 != nullptr) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t[r] += s.r1[r];
+    }
+    if (R2 && p.res2 != nullptr) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t[r] += s.r2[r >> 1];
+    }
+    if (p.post_relu) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) t[r] = fmaxf(t[r], 0.f);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) buf_st1_stream(rs_y, vo_y, (((r & 3) + 8 * (r >> 2)) * p.ldy + j * 32) * 4, t[r]);
+  }
+};
+
+// conv_epilogue's direct path: absent (the caller finishes its direct tiles itself), the whole tile with the flags
+// selected per element (the split-bf16 and halo kernels: their register budgets are tuned around this form), or the
+// whole tile through EpiDirect::finish
+enum { kDirectNone = 0, kDirectWhole = 1, kDirectSlices = 2 };
+
 struct EpiNoHook {
   __device__ __forceinline__ void operator()() const {}
 };
@@ -137,7 +246,8 @@ struct EpiNoHook {
 // CHROWS > 0: the row loop of the LDS-slab path runs in chunks of CHROWS iterations, each chunk loading ITS residual rows
 // first (instead of every residual row of the block before the first store): a kernel whose accumulators leave few
 // registers (the split-bf16 wide tiling holds 96 of them for its other column slice) does not spill.
-template <int WM, int WN, int TM, int TN, bool UP2, bool PRE, typename HOOK = EpiNoHook, bool DIRECT_R2 = true, int CHROWS = 0>
+template <int WM, int WN, int TM, int TN, bool UP2, bool PRE, typename HOOK = EpiNoHook, bool DIRECT_R2 = true, int CHROWS = 0,
+          int DIRECT = kDirectWhole>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[TM][TN], float* smem, int m0,
                                               int n0, int M, int epi_vec, const EpiPrefetch<TM, TN>& pre,
                                               HOOK staged = HOOK()) {
@@ -153,57 +263,75 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[T
   constexpr bool kPre = PRE && EpiPrefetch<TM, TN>::kEnabled;
   constexpr bool kPool = tile_pools_in_pairs(WM, TM, UP2);           // (gemm_family.h: the route asks the same functions)
   constexpr bool kPoolWave = tile_pools_in_wave(TM, UP2);
-  if constexpr (!UP2 && kPre && std::is_same<HOOK, EpiNoHook>::value) {
+  if constexpr (DIRECT != kDirectNone && !UP2 && kPre && std::is_same<HOOK, EpiNoHook>::value) {
     if (EpiPrefetch<TM, TN>::template direct_tile<WM, WN>(p, m0, n0, M, epi_vec)) {
-      // Direct path (interior tiles of plain launches): no LDS staging, no work-group barrier, no wait between the last
-      // MFMA and the first store.  Register r of a lane is one row of one column: a store instruction writes two
-      // 128-byte row segments, BN scale / shift are one value per lane and column tile, the row step is a scalar offset.
-      const auto rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)(((unsigned)(M - 1) * p.ldy + (unsigned)p.Cout) * 4u),
-                                                          0x00020000);
-      const int ncol = n0 + wn * TN * 32 + li;
-      const int vo = ((m0 + wm * TM * 32 + 4 * lh) * p.ldy + ncol) * 4;
-      float sc[TN], sh[TN];
+      if constexpr (DIRECT == kDirectSlices) {
+        // The same through the slice functions the fp32 LDS-DMA GEMM finishes its peeled tiles with (flags tested once per
+        // slice).  The residual tile is in flight already (EpiPrefetch::issue); the half-resolution second
+        // residual of every slice is requested before the first slice is finished.
+        const EpiDirect<WM, WN, TN, DIRECT_R2> epi(p, m0, n0, M);
+        EpiSlice sl[TN];
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        sc[j] = pre.dsc[j];
-        sh[j] = pre.dsh[j];
+        for (int j = 0; j < TN; ++j) {
+          sl[j].sc = pre.dsc[j];
+          sl[j].sh = pre.dsh[j];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sl[j].r1[r] = f4c(pre.r1[0][j * 4 + (r >> 2)], r & 3);
+          epi.request_res2(p, j, sl[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) epi.finish(p, j, acc[0][j], sl[j]);
+      } else {
+        // Direct path (interior tiles of plain launches): no LDS staging, no work-group barrier, no wait between the last
+        // MFMA and the first store.  Register r of a lane is one row of one column: a store instruction writes two
+        // 128-byte row segments, BN scale / shift are one value per lane and column tile, the row step is a scalar offset.
+        const auto rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)(((unsigned)(M - 1) * p.ldy + (unsigned)p.Cout) * 4u),
+                                                            0x00020000);
+        const int ncol = n0 + wn * TN * 32 + li;
+        const int vo = ((m0 + wm * TM * 32 + 4 * lh) * p.ldy + ncol) * 4;
+        float sc[TN], sh[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          sc[j] = pre.dsc[j];
+          sh[j] = pre.dsh[j];
+        }
+        // Second residual at HALF resolution (res2_down; the launcher only sets the flag on maps of 2^a x 2^b >= 32 pixels
+        // with OW >= 8): the wave's 32 pixels start at an even image row, so with t = (r & 3) + 8 * (r >> 2) + 4 * lh the
+        // source pixel splits into a wave-uniform part per register r and 2 * lh * ldr2 per lane -- again no vector ALU.
+        // Registers r and r ^ 1 of a lane read the same source pixel: 8 loads per column tile.
+        float r2[DIRECT_R2 ? TN : 1][8];
+        if (DIRECT_R2 && p.res2 != nullptr) {                                   // (uniform) direct tiles carry res2 only as res2_down
+          const auto rs_2 = __builtin_amdgcn_make_buffer_rsrc(
+              const_cast<float*>(p.res2), 0, (int)(((unsigned)((M >> 2) - 1) * p.ldr2 + (unsigned)p.Cout) * 4u), 0x00020000);
+          const int ohw = p.OH * p.OW, ow_sh = __ffs(p.OW) - 1;
+          const int mb = __builtin_amdgcn_readfirstlane(m0 + wm * 32);
+          const int fr = mb >> (__ffs(ohw) - 1), pos = mb & (ohw - 1);
+          const int oh0 = pos >> ow_sh, ow0 = pos & (p.OW - 1);
+          const int v2 = (2 * lh * p.ldr2 + ncol) * 4;
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int h = 0; h < 8; ++h) {
+              const int tr = 2 * (h & 1) + 8 * (h >> 1);              // rows (2h, 2h + 1) -> registers r = 2h, 2h + 1
+              const int oh = oh0 + (tr >> ow_sh), ow = ow0 + (tr & (p.OW - 1));
+              const int src = (fr * (p.OH >> 1) + (oh >> 1)) * (p.OW >> 1) + (ow >> 1);
+              r2[j][h] = buf_ld1_stream(rs_2, v2, (src * p.ldr2 + j * 32) * 4);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              float t = acc[i][j][r];
+              if (p.post_scale != nullptr) t = t * sc[j] + sh[j];
+              if (p.res1 != nullptr) t += f4c(pre.r1[i][j * 4 + (r >> 2)], r & 3);
+              if (DIRECT_R2 && p.res2 != nullptr) t += r2[DIRECT_R2 ? j : 0][r >> 1];
+              if (p.post_relu) t = fmaxf(t, 0.f);
+              buf_st1_stream(rs_y, vo, ((i * 32 + (r & 3) + 8 * (r >> 2)) * p.ldy + j * 32) * 4, t);
+            }
       }
-      // Second residual at HALF resolution (res2_down; the launcher only sets the flag on maps of 2^a x 2^b >= 32 pixels
-      // with OW >= 8): the wave's 32 pixels start at an even image row, so with t = (r & 3) + 8 * (r >> 2) + 4 * lh the
-      // source pixel splits into a wave-uniform part per register r and 2 * lh * ldr2 per lane -- again no vector ALU.
-      // Registers r and r ^ 1 of a lane read the same source pixel: 8 loads per column tile.
-      float r2[DIRECT_R2 ? TN : 1][8];
-      if (DIRECT_R2 && p.res2 != nullptr) {                                   // (uniform) direct tiles carry res2 only as res2_down
-        const auto rs_2 = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.res2), 0, (int)(((unsigned)((M >> 2) - 1) * p.ldr2 + (unsigned)p.Cout) * 4u), 0x00020000);
-        const int ohw = p.OH * p.OW, ow_sh = __ffs(p.OW) - 1;
-        const int mb = __builtin_amdgcn_readfirstlane(m0 + wm * 32);
-        const int fr = mb >> (__ffs(ohw) - 1), pos = mb & (ohw - 1);
-        const int oh0 = pos >> ow_sh, ow0 = pos & (p.OW - 1);
-        const int v2 = (2 * lh * p.ldr2 + ncol) * 4;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int h = 0; h < 8; ++h) {
-            const int tr = 2 * (h & 1) + 8 * (h >> 1);              // rows (2h, 2h + 1) -> registers r = 2h, 2h + 1
-            const int oh = oh0 + (tr >> ow_sh), ow = ow0 + (tr & (p.OW - 1));
-            const int src = (fr * (p.OH >> 1) + (oh >> 1)) * (p.OW >> 1) + (ow >> 1);
-            r2[j][h] = buf_ld1_stream(rs_2, v2, (src * p.ldr2 + j * 32) * 4);
-          }
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float t = acc[i][j][r];
-            if (p.post_scale != nullptr) t = t * sc[j] + sh[j];
-            if (p.res1 != nullptr) t += f4c(pre.r1[i][j * 4 + (r >> 2)], r & 3);
-            if (DIRECT_R2 && p.res2 != nullptr) t += r2[DIRECT_R2 ? j : 0][r >> 1];
-            if (p.post_relu) t = fmaxf(t, 0.f);
-            buf_st1_stream(rs_y, vo, ((i * 32 + (r & 3) + 8 * (r >> 2)) * p.ldy + j * 32) * 4, t);
-          }
       return;
     }
   }

@@ -27,6 +27,23 @@ __device__ __forceinline__ void fetch_frags(const unsigned (&a_addr)[TM][4], uns
   if constexpr (TN > 2) fb[2] = lds_rd<BO + 1024>(b_addr);
 }
 
+// f(std::integral_constant<int, I>{}) for I in [I0, N): an unrolled loop whose index is a constant expression (asm offsets)
+template <int I0, int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I0 < N) {
+    f(std::integral_constant<int, I0>{});
+    static_for<I0 + 1, N>(f);
+  }
+}
+
+// at most N of the asm ds_reads are still in flight (they return in order): the older ones have landed
+template <int N>
+__device__ __forceinline__ void lgkm_wait_n() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 // KXK: the same kernel as an implicit GEMM over a K x K (strided, zero-padded) convolution whose Cin is a multiple
 // of 32: K-step kt covers 32 channels of ONE filter tap, so each staged row is still one contiguous 128-byte run -- of
 // the tap's input pixel, or of a page of zeros when the tap falls into the padding (ReLU-on-load keeps zeros zero).
@@ -187,10 +204,15 @@ __device__ __forceinline__ void gemm1x1_body(const ConvArgs& p, const int epi_ve
   // (Fetching tile kt+1's first fragments before the loop back-edge was tried: correct with a tail wait, but
   // the loop-carried fragment registers cost more than the hidden LDS latency buys: 111 vs 118 TFLOP/s.)
   EpiPrefetch<TM, TN> pre;
-  for (int kt = 0; kt < nk; ++kt) {
+  // Direct tiles of the one-row-block tilings (gemm_family.h: tile_epi_sliced) leave the loop one K-step early: the last
+  // step runs column tile by column tile below, each tile finished under the next one's MFMAs.
+  constexpr bool kSliced = tile_epi_sliced(GemmTile{WM, WN, TM, TN}, PRE, KXK) && !UP2 && !D2S;
+  const bool sliced = kSliced && EpiPrefetch<TM, TN>::template direct_tile<WM, WN>(p, m0, n0, M, epi_vec);
+  const int nloop = sliced ? nk - 1 : nk;
+  for (int kt = 0; kt < nloop; ++kt) {
     const int cur = kt & 1;
     if constexpr (!D2S) {             // (D2S reads its residual at the output resolution, in its own epilogue)
-      if (kt == nk - 1) pre.template issue<WM, WN>(p, m0, n0, M, epi_vec);   // lands during the last MFMA block
+      if (kt == nk - 1) pre.template issue<WM, WN, !kSliced>(p, m0, n0, M, epi_vec);   // lands during the last MFMA block
     }
     const unsigned so = (unsigned)(cur * STAGE * 4);
     unsigned a_addr[TM][4];
@@ -236,8 +258,76 @@ __device__ __forceinline__ void gemm1x1_body(const ConvArgs& p, const int epi_ve
     __syncthreads();
   }
 
+  if constexpr (kSliced) {
+    if (sliced) {
+      // ---- the last K-step, column-major: the wave's TN accumulator tiles are independent, so issuing their MFMAs tile by
+      // tile changes no bit (each element still accumulates k ascending) and tile j's BN / residual VALU and its 16
+      // stores drain under tile j + 1's 16 MFMAs; only the last tile's finish is exposed.  All four sub-steps' A
+      // fragments are read (and BN'd / ReLU'd) once; tile j + 1's B fragments land in the registers tile j's leave.
+      // Every fragment read is awaited before the next branch (the NB above): request() and finish() branch on the
+      // launch's flags.
+      const int kt = nk - 1;
+      const unsigned so = (unsigned)((kt & 1) * STAGE * 4);
+      const unsigned b_addr = b_base + so;
+      const unsigned t_sc = t_sc0 + (unsigned)(kt * BK * 4), t_sh = t_sc + (unsigned)(p.Kp * 4);
+      const EpiDirect<WM, WN, TN> epi(p, m0, n0, M);
+      EpiSlice sl[2];                                  // at most two slices' residuals in flight: slice j + 1's are
+      epi.request(p, 0, sl[0]);                        // requested before slice j's MFMAs, slice 0's here
+      float4 fa[4][1], fb[4], sc[4], sh[4];
+      auto read_a = [&](auto sc_) {
+        constexpr int S = decltype(sc_)::value;
+        fa[S][0] = lds_rd<0>(a_base[0][S] + so);
+        fetch_affine<PRE, S>(t_sc, t_sh, sc[S], sh[S]);
+      };
+      auto read_b0 = [&](auto sc_) {
+        constexpr int S = decltype(sc_)::value;
+        fb[S] = lds_rd<BOFF + S * 2 * BN * 16>(b_addr);
+      };
+      if constexpr (PRE) {
+        // the scale / shift fragments need registers too: one sub-step's reads (three) run ahead of the sub-step being
+        // BN'd -- LDS reads return in order, so a counted wait releases the older ones
+        read_a(std::integral_constant<int, 0>{});
+        static_for<0, 3>([&](auto sc_) {
+          constexpr int S = decltype(sc_)::value;
+          read_a(std::integral_constant<int, S + 1>{});
+          lgkm_wait_n<3>();
+          relu_frags(fa[S], sc[S], sh[S]);
+        });
+        static_for<0, 4>(read_b0);
+        lgkm_wait_n<4>();
+        relu_frags(fa[3], sc[3], sh[3]);
+        lgkm_wait();
+      } else {
+        static_for<0, 4>(read_a);
+        static_for<0, 4>(read_b0);
+        lgkm_wait();
+        static_for<0, 4>([&](auto sc_) { relu_frags(fa[decltype(sc_)::value], sc[0], sh[0]); });
+      }
+      static_for<0, TN>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        if constexpr (J + 1 < TN) epi.request(p, J + 1, sl[(J + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<0, 4>([&](auto sc_) {
+          constexpr int S = decltype(sc_)::value;
+          acc[0][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S][0].x, fb[S].x, acc[0][J], 0, 0, 0);
+          acc[0][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S][0].y, fb[S].y, acc[0][J], 0, 0, 0);
+          acc[0][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S][0].z, fb[S].z, acc[0][J], 0, 0, 0);
+          acc[0][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S][0].w, fb[S].w, acc[0][J], 0, 0, 0);
+          if constexpr (J + 1 < TN) {
+            __builtin_amdgcn_sched_barrier(0);         // the read follows the MFMAs whose operand registers it takes over
+            fb[S] = lds_rd<BOFF + S * 2 * BN * 16 + (J + 1) * 512>(b_addr);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        });
+        if constexpr (J + 1 < TN) lgkm_wait();
+        epi.finish(p, J, acc[0][J], sl[J & 1]);
+      });
+      return;
+    }
+  }
+  constexpr int kDirect = kSliced ? kDirectNone : kDirectSlices;   // (the direct tiles of a sliced kernel have left above)
   if constexpr (D2S) d2s_epilogue<WM, WN, TM, TN>(p, acc, smem, m0, n0, M, epi_vec, cb);
-  else conv_epilogue<WM, WN, TM, TN, UP2, true>(p, acc, smem, m0, n0, M, epi_vec, pre);
+  else conv_epilogue<WM, WN, TM, TN, UP2, true, EpiNoHook, true, 0, kDirect>(p, acc, smem, m0, n0, M, epi_vec, pre);
 }
 
 }  // namespace dh

@@ -74,6 +74,15 @@ constexpr bool tile_pools_in_pairs(int WM, int TM, bool UP2 = false) { return TM
 // never straddles frames and starts at an even row) -- the wave pools its own slab, no partner needed: any TM == 1 tiling.
 constexpr bool tile_pools_in_wave(int TM, bool UP2 = false) { return TM == 1 && !UP2; }
 constexpr bool tile_pools_for(const GemmTile& t, int OW) { return OW == 32 ? tile_pools_in_pairs(t.wm, t.tm) : tile_pools_in_wave(t.tm); }
+// The fp32 LDS-DMA GEMM finishes its direct tiles column tile by column tile under the last K-step's MFMAs (gemm1x1_body.h):
+// a wave with ONE row block holds TN independent accumulator tiles and has the registers for two residual slices.  The
+// compile-time switch: a kernel taken out here keeps the whole-tile direct epilogue -- every tiling gives the same bits.
+// Taken out: the forms whose K loop carries the most state at the narrow tilings (BN prologue below three column tiles, the
+// K x K form of the one-wave tiling), where the peeled step would cost a wave per SIMD of occupancy
+// (profiles/epilogue_slices.md).
+constexpr bool tile_epi_sliced(const GemmTile& t, bool PRE = false, bool KXK = false) {
+  return t.tm == 1 && !(PRE && t.tn < 3) && !(KXK && t.wm == 1 && t.tn == 1);
+}
 // the fused up-sampling epilogue: six 32 x 32 accumulators per wave would spill beside it (the wide tiling holds them in halves)
 constexpr bool tile_has_up2(const GemmTile& t) { return t.wide || t.tm * t.tn < 6; }
 // the wide tiling: with fewer than three parts its fixed half-tile choreography has nothing left to hide the operand traffic
